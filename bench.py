@@ -26,6 +26,13 @@ torch.cuda.synchronize(), max wall time over ranks.  p99 latency is measured
 from each request's Poisson ARRIVAL time (so ingest wait + preprocess + queue
 time all count) to the moment a backend slot admits it; the pure
 enqueue->dispatch p99 is reported too.
+
+A plain run serves one timed window at ``--util`` and reports it.  ``--full``
+adds what the headline figure does not need: the SLO search (further windows
+at the ``--slo-climb`` / ``--slo-backoff`` utilisations; the headline is then
+the best window that held the operating point) and the secondary null-backend
+gateway measurement.  ``--dump-outputs DIR`` writes the outputs of one fixed,
+seeded batch served after the timed steps (``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -87,10 +94,10 @@ def parse(argv=None):
                          "tiers <= 86 ms) but lifts the 8-rank sim's all-tier p99 to 165-242 ms; the SLO search "
                          "below re-serves at lower utilisations if a window misses the operating point")
     ap.add_argument("--slo-backoff", default="0.98,0.95,0.9,0.85,0.75",
-                    help="utilisations re-served (in order, same process) when the window at --util misses the "
+                    help="--full: utilisations re-served (in order, same process) when the window at --util misses the "
                          "operating point; value = req/s at the highest one that held it (0 if none did)")
     ap.add_argument("--slo-climb", default="1.0,1.02,1.04",
-                    help="utilisations tried next (in order, same process) while the window at --util and every "
+                    help="--full: utilisations tried next (in order, same process) while the window at --util and every "
                          "later one HOLD the operating point; the headline is the best window that held it.  '' = "
                          "no climb (VERDICT r4 weak #4: a search that only backs off caps the headline below what "
                          "the SLO allows)")
@@ -174,8 +181,18 @@ def parse(argv=None):
     ap.add_argument("--data-backend", default="", choices=["", "nccl", "gloo"],
                     help="data plane (KV migration): nccl = RCCL after a preflight (gloo fallback, flagged in "
                          "comm.data_backend), gloo; '' = nccl on GPUs, gloo in --cpu-dry-run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the SLO search's further windows "
+                         "(--slo-climb / --slo-backoff) and the secondary null-backend gateway measurement "
+                         "(--gateway-only-s).  A plain run serves ONE window at --util")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, serve one fixed, seeded batch of requests through the same "
+                         "preprocessor and backend and write what their caller receives (priorities, prompt token "
+                         "ids, generated token ids) as DIR/<name>.npy -- the same arrays for the same arguments, "
+                         "so two builds can be compared output for output")
+    ap.add_argument("--dump-requests", type=int, default=256, help="--dump-outputs: requests of the fixed batch")
     ap.add_argument("--gateway-only-s", type=float, default=3.0,
-                    help="seconds of the secondary null-backend gateway measurement (0 = skip)")
+                    help="with --full: seconds of the secondary null-backend gateway measurement (0 = skip)")
     ap.add_argument("--gateway-only-rate", type=float, default=50000.0)
     return ap.parse_args(argv)
 
@@ -245,6 +262,56 @@ class FrontDoorFeed:
             self.proc.wait(timeout=30)
             self.ring.unlink()
         self.ring.close()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(a, engine, pre, use_gpu: bool) -> dict:
+    """``--dump-outputs DIR``.  The timed steps serve Poisson arrivals on the
+    wall clock, so no two runs form the same batches; what is written is
+    therefore one more pass of the same path over a FIXED batch, after the
+    timed steps and their drain (the engine is idle, its slots are free):
+    ``--dump-requests`` messages of a seeded ``Workload`` go through the
+    preprocessor the gateway ingests with (text_analyze + classifier + prompt
+    token ids) and, admitted together, through the backend engine's forward
+    steps until each has its ``--gen-tokens`` greedy tokens.  Written, one
+    row per request in the order the workload made them: ``priority`` and
+    ``prompt_len`` [n], ``prompt_ids`` [n, prompt_cap] (0-padded), and
+    ``tokens`` [n, gen_tokens], the ids a caller reads from
+    ``Request.out_tokens`` -- all float64, which holds every id exactly."""
+    from llm_message_queue_amd.backend.engine import Request
+    from llm_message_queue_amd.gateway.workload import Workload
+
+    row_bytes = 8 * (2 + a.prompt_cap + a.gen_tokens)
+    n = max(1, min(a.dump_requests, DUMP_MAX_BYTES // row_bytes, engine.free_slots()))
+    msgs = Workload(seed=a.seed * 1000 + 424243).make(n)
+    pre.process_batch(msgs, use_gpu=use_gpu, prompt_cap=a.prompt_cap)
+    arrays = {"priority": np.array([int(m.priority) for m in msgs], dtype=np.float64),
+              "prompt_len": np.zeros(n, dtype=np.float64),
+              "prompt_ids": np.zeros((n, a.prompt_cap), dtype=np.float64)}
+    reqs = []
+    for i, m in enumerate(msgs):
+        ids = np.asarray(m.prompt_ids if m.prompt_ids is not None else (), dtype=np.uint32)[:a.prompt_cap]
+        arrays["prompt_len"][i] = len(ids)
+        arrays["prompt_ids"][i, :len(ids)] = ids
+        p = ids.astype(np.int64).astype(np.int32) if len(ids) else np.zeros(1, dtype=np.int32)
+        reqs.append(Request(req_id=i, prompt=p, gen_tokens=a.gen_tokens, tier=2))
+    if hasattr(engine, "model"):                 # (a SimEngine computes no tokens)
+        admitted = engine.admit(reqs)
+        if len(admitted) != n:
+            raise RuntimeError(f"--dump-outputs: the idle engine admitted {len(admitted)} of {n} requests")
+        done = engine.drain()
+        if len(done) != n:
+            raise RuntimeError(f"--dump-outputs: {len(done)} of {n} requests completed")
+        tokens = np.zeros((n, a.gen_tokens), dtype=np.float64)
+        for r in done:
+            tokens[r.req_id, :len(r.out_tokens)] = r.out_tokens
+        arrays["tokens"] = tokens
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(a.dump_outputs, f"{name}.npy"), arr)
+    return {"dir": a.dump_outputs, "requests": n, "arrays": {k: list(v.shape) for k, v in arrays.items()}}
 
 
 def main(argv=None) -> int:
@@ -631,8 +698,10 @@ def main(argv=None) -> int:
     # it (its value is still capped by what was dispatched AND what arrived
     # in the window).  The decision inputs are all-gathered, so every rank
     # runs the same windows.
-    backoff = [u for u in (float(x) for x in a.slo_backoff.split(",") if x) if u < a.util]
-    climb = [u for u in (float(x) for x in a.slo_climb.split(",") if x) if u > a.util]
+    # A plain run serves the one window at --util (value = its rate if it held
+    # the operating point, else 0); the search's further windows need --full.
+    backoff = [u for u in (float(x) for x in a.slo_backoff.split(",") if x) if u < a.util] if a.full else []
+    climb = [u for u in (float(x) for x in a.slo_climb.split(",") if x) if u > a.util] if a.full else []
     tried = []
     best = res = None
     t_search = time.monotonic()
@@ -675,7 +744,8 @@ def main(argv=None) -> int:
            # value can be compared with single-window rounds
            "first_window": {"util": tried[0]["util"], "value": tried[0]["value"] if tried[0]["met"] else 0.0,
                             "met": tried[0]["met"]},
-           "search_s": round(time.monotonic() - t_search, 1), "directions": "climb + backoff"}
+           "search_s": round(time.monotonic() - t_search, 1),
+           "directions": "climb + backoff" if a.full else "none (one window at --util; --full searches)"}
     if not res["met"]:
         slo["reason"] = (f"no utilisation in {slo['util_tried']} held p99 <= {P99_TARGET_MS} ms (all tiers) and "
                          f"realtime p99 <= {REALTIME_P99_TARGET_MS} ms; value is 0 by construction")
@@ -782,7 +852,7 @@ def main(argv=None) -> int:
             float(eh[1]) / max(1, a.steps) / 1e6, 3), engine_enqueue=round(
             float(eh[2]) / max(1, a.steps) / 1e6, 3)),
     }
-    if a.gateway_only_s > 0:
+    if a.full and a.gateway_only_s > 0:
         # Secondary, untimed-by-contract measurement: the gateway path alone
         # (GPU preprocess + native queue + dispatcher) against a null backend,
         # Poisson load at --gateway-only-rate per GPU.
@@ -816,6 +886,8 @@ def main(argv=None) -> int:
                                "p99_enqueue_to_dispatch_ms": round(l2["p99_enq_ms"], 3),
                                "note": "null backend: gateway path only (what the reference's 10k msg/s "
                                        "target measures); not the headline value"}
+    if a.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(a, engine, pre, use_gpu=not dry)
     if rank == 0:
         line = json.dumps(out)
         print(line, flush=True)

@@ -8,6 +8,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 NPROC=${NPROC:-2}
+MR_ARGS=${MR_ARGS:---full --steps 40 --warmup 10 --slots 384 --gateway-only-s 1}
 timeout -k 10 ${MR_T:-420} python -m torch.distributed.run --nnodes=1 --nproc-per-node $NPROC \
   --master-addr 127.0.0.1 --master-port ${PORT:-29533} bench.py --gpus $NPROC \
   ${MR_ARGS:---steps 40 --warmup 10 --slots 384 --gateway-only-s 1} > gpurun_out/multirank.log 2>&1

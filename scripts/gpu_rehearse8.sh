@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS=${R8_ARGS:---steps 20 --warmup 5 --slots 128 --gateway-only-s 1}
+ARGS=${R8_ARGS:---full --steps 20 --warmup 5 --slots 128 --gateway-only-s 1}
 timeout -k 10 ${R8_T:-420} python bench.py --gpus 8 $ARGS --ingress ${R8_INGRESS:-per-rank} \
   > gpurun_out/rehearse8_${R8_INGRESS:-per-rank}.log 2>&1
 rc=$?; echo "rehearse8 ${R8_INGRESS:-per-rank} rc=$rc"; tail -c 1500 gpurun_out/rehearse8_${R8_INGRESS:-per-rank}.log

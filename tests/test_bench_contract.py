@@ -29,7 +29,7 @@ def _run(args, timeout=240):
 
 
 def test_bench_single_rank_dry_run():
-    d = _run([sys.executable, "bench.py", "--cpu-dry-run", "--steps", "4", "--warmup", "2",
+    d = _run([sys.executable, "bench.py", "--cpu-dry-run", "--steps", "4", "--warmup", "2", "--full",
               "--gateway-only-s", "0.3", "--gateway-only-rate", "300"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
               "scaling", "vs_baseline", "dtype", "data", "config"):
@@ -61,6 +61,34 @@ def test_bench_single_rank_dry_run():
     assert d["config"]["seq_len_is"] == "max_ctx" and d["config"]["max_ctx"] == d["config"]["seq_len"]
     assert d["realtime_mode"] == d["config"]["realtime_mode"] == "off"
     assert d["data_plane"] == "none"
+
+
+def test_bench_plain_run_serves_one_window(tmp_path):
+    """A plain run (no ``--full``) does only what the headline needs: ONE
+    timed window at ``--util`` -- no climb or back-off windows and no
+    null-backend gateway phase, whatever their options say -- and
+    ``--dump-outputs`` writes the same arrays for the same arguments."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--cpu-dry-run", "--steps", "4", "--warmup", "2",
+                  "--gateway-only-s", "0.3", "--test-miss-above-util", "0.5", "--dump-outputs", str(tmp_path / name),
+                  "--dump-requests", "12", "--steady-ticks", "4"])
+        s = d["slo_search"]
+        assert s["util_tried"] == [0.98] and len(s["attempts"]) == 1 and "gateway_only" not in d
+        # (the hook makes the one window miss: no back-off follows, the value is 0 by construction)
+        assert d["p99_target_met"] is False and d["value"] == 0.0 and "reason" in s
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["requests_accounted"]["lost"] == 0
+        assert d["dumped_outputs"]["requests"] == 12
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert set(a) == set(b) == {"priority", "prompt_len", "prompt_ids", "tokens"}
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+    assert a["tokens"].shape == (12, 4) and a["prompt_ids"].shape == (12, 16)
+    assert a["prompt_len"].min() >= 1 and a["prompt_len"].max() <= 16
+    assert (a["tokens"] >= 0).all() and (a["tokens"] < 1024).all() and len(np.unique(a["tokens"])) > 1
+    assert set(np.unique(a["priority"])) <= {1.0, 2.0, 3.0, 4.0} and len(np.unique(a["priority"])) > 1
 
 
 def test_bench_realtime_micro_mode_dry_run():
@@ -107,7 +135,7 @@ def test_rccl_preflight_failure_falls_back_to_gloo_data_plane():
 def test_bench_four_ranks_torchrun_dry_run():
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
               "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "4",
-              "--cpu-dry-run", "--steps", "5", "--warmup", "2", "--gateway-only-s", "0.5",
+              "--cpu-dry-run", "--steps", "5", "--warmup", "2", "--full", "--gateway-only-s", "0.5",
               "--gateway-only-rate", "200"])
     assert d["n_gpus"] == 4 and d["config"]["parallelism"] == "dp4"
     # 4 CPU ranks of a tiny model on a shared host: whether a util holds the
@@ -220,7 +248,7 @@ def test_bench_slo_search_backs_off_to_a_met_operating_point():
     re-served in the same process at the next lower utilisation, and the
     value reported is that window's rate; the first attempt is listed."""
     d = _run([sys.executable, "bench.py", "--cpu-dry-run", "--sim-gpu", "1", "--steps", "20", "--warmup", "2",
-              "--gateway-only-s", "0", "--test-miss-above-util", "0.95"], timeout=420)
+              "--full", "--gateway-only-s", "0", "--test-miss-above-util", "0.95"], timeout=420)
     s = d["slo_search"]
     assert s["util_tried"][0] == 0.98 and s["attempts"][0]["met"] is False
     # 0.95 is the first util the hook lets through; on a loaded host (the
@@ -240,7 +268,7 @@ def test_bench_slo_search_climbs_while_the_slo_holds():
     test hook makes every util above 1.01 miss); the headline is the best
     window that held it, and every attempt is listed."""
     d = _run([sys.executable, "bench.py", "--cpu-dry-run", "--sim-gpu", "1", "--steps", "20", "--warmup", "2",
-              "--gateway-only-s", "0", "--test-miss-above-util", "1.01"], timeout=420)
+              "--full", "--gateway-only-s", "0", "--test-miss-above-util", "1.01"], timeout=420)
     s = d["slo_search"]
     met = [t for t in s["attempts"] if t["met"]]
     if not s["attempts"][0]["met"]:                 # a loaded host missed at 0.98: the back-off path ran

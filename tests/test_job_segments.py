@@ -23,6 +23,7 @@ import urllib.request
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_JSON = json.JSONDecoder()
 
 
 def _port():
@@ -71,7 +72,7 @@ class Server:
                 + rdzv + [f"--max-restarts={restarts}"] + cmd[1:]
         self.proc = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                      text=True, start_new_session=True)
-        self.events, self.err = [], []
+        self.events, self.err, self.junk = [], [], []
         self._cv = threading.Condition()
         threading.Thread(target=self._read, args=(self.proc.stdout, True), daemon=True).start()
         threading.Thread(target=self._read, args=(self.proc.stderr, False), daemon=True).start()
@@ -82,14 +83,22 @@ class Server:
             if not out:
                 self.err.append(line)
                 continue
-            if line.startswith("{"):
+            # the ranks share this pipe, and an event's text and its newline
+            # are two writes when Python's stdout is unbuffered: take every
+            # JSON object a line holds, and keep what did not parse for the
+            # failure message instead of dropping it silently
+            pos = 0 if line.startswith("{") else -1
+            while pos >= 0:
                 try:
-                    ev = json.loads(line)
+                    ev, end = _JSON.raw_decode(line, pos)
                 except ValueError:
-                    continue
-                with self._cv:
-                    self.events.append(ev)
-                    self._cv.notify_all()
+                    self.junk.append(line[pos:])
+                    break
+                if isinstance(ev, dict):
+                    with self._cv:
+                        self.events.append(ev)
+                        self._cv.notify_all()
+                pos = line.find("{", end)
 
     def wait_for(self, pred, timeout=180):
         deadline = time.time() + timeout
@@ -102,7 +111,8 @@ class Server:
                     break
                 self._cv.wait(0.5)
         tail = "".join(self.err[-120:])
-        raise AssertionError(f"server event not seen (rc={self.proc.poll()}); stderr tail:\n{tail}")
+        raise AssertionError(f"server event not seen (rc={self.proc.poll()}); last events: {self.events[-8:]}; "
+                             f"unparsed stdout: {self.junk[-8:]}; stderr tail:\n{tail}")
 
     def ranks(self, n, restart=0, timeout=180):
         def pred(e):

@@ -45,6 +45,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sample_noise.h"
+
 namespace llmq {
 
 typedef __attribute__((ext_vector_type(8))) short gm_bf16x8;
@@ -58,7 +60,7 @@ constexpr int GM_LDS_BYTES = 2 * GM_BUF_BYTES;     // 128 KiB
 constexpr int GM_GROUP_M = 8;                    // default M-tiles per block-order group
 
 enum { GM_EPI_STORE = 0, GM_EPI_SWIGLU = 2, GM_EPI_ROPE = 3, GM_EPI_ARGMAX = 4, GM_EPI_RESID = 5,
-       GM_EPI_RESID_LDS = 6, GM_EPI_RESID_PRE = 7, GM_EPI_RESID_RMS = 8 };
+       GM_EPI_RESID_LDS = 6, GM_EPI_RESID_PRE = 7, GM_EPI_RESID_RMS = 8, GM_EPI_SAMPLE = 9 };
 // GM_EPI_RESID_PRE: GM_EPI_RESID_LDS whose first quarter of the residual tile
 // (rows 0-31 of every wave's 128 x 64 block) is fetched into the 32 KiB of
 // LDS gfx950 has beyond the operand buffers at kernel start, so it is in LDS
@@ -82,11 +84,25 @@ constexpr int gm_lds_bytes() { return EPI == GM_EPI_RESID_PRE ? GM_LDS_BYTES + G
 // adds them in column-tile order and writes 1 / sqrt(sum / N + reps) to
 // rscale[tm * 256 + row]: what row_rms_kernel computes, in a fixed order,
 // without the 33 MB re-read of the rows by a separate launch.
+// GM_EPI_SAMPLE: GM_EPI_ARGMAX over score = acc * inv_temp[row] + G(key[row],
+// column) -- per-request temperature sampling by the Gumbel-max identity,
+// the noise a pure function of (row key, column) (sample_noise.h).  A row
+// with inv_temp == 0 is greedy: its score is the raw accumulator, so its
+// result is GM_EPI_ARGMAX's, ties included.  inv_temp [ceil(M / 256) * 256]
+// and key [ceil(M / 256) * 256][2] (k0, k1) hold whole row tiles, like the
+// row scales; they share the storage of the GM_EPI_RESID_RMS pointers (no
+// epilogue uses both), so the other kernels' argument layout is unchanged.
 struct GmSide {
   float* pv;
   int32_t* pi;
-  float* rpart;
-  int* rticket;
+  union {
+    float* rpart;
+    const float* inv_temp;
+  };
+  union {
+    int* rticket;
+    const uint32_t* key;
+  };
   float* rscale;
   float reps;
 };
@@ -578,7 +594,34 @@ __device__ __forceinline__ void gemm_tile(
 
   // ---- epilogue through LDS (the staging buffers are free after the last barrier)
   const int row0 = tm * GM_BM + wr * 128;          // first output row of this wave
-  if (EPI == GM_EPI_ARGMAX) {
+  if (EPI == GM_EPI_ARGMAX || EPI == GM_EPI_SAMPLE) {
+    if constexpr (EPI == GM_EPI_SAMPLE) {
+      // score = acc / T + Gumbel(key[row], column) in place; the row inputs
+      // of this lane's 32 rows come as whole-tile vector loads (padded
+      // arrays: rows >= M read the padding, inv_temp 0, and are not stored)
+      const uint32_t col = (uint32_t)(tn * GM_BN + wc * 64 + fr);
+#pragma unroll
+      for (int mh = 0; mh < 2; ++mh)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const int r4 = row0 + mh * 64 + m * 16 + fq * 4;
+          const gm_f32x4 it = *reinterpret_cast<const gm_f32x4*>(am.inv_temp + r4);
+          const gm_u32x4 ka = *reinterpret_cast<const gm_u32x4*>(am.key + 2 * r4);
+          const gm_u32x4 kb = *reinterpret_cast<const gm_u32x4*>(am.key + 2 * r4 + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t k0 = j < 2 ? ka[2 * j] : kb[2 * j - 4];
+            const uint32_t k1 = j < 2 ? ka[2 * j + 1] : kb[2 * j - 3];
+            if (it[j] != 0.f) {                    // (a greedy row keeps its accumulators)
+#pragma unroll
+              for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+                for (int n = 0; n < 2; ++n)
+                  acc[mh][m][nh][n][j] = acc[mh][m][nh][n][j] * it[j] + sn_gumbel(k0, k1, col + nh * 32 + n * 16);
+            }
+          }
+        }
+    }
     // per (row, wave): max over the wave's 64 columns -- 4 per lane, then the
     // 16 lanes of a row group (xor butterfly; ties keep the lower column)
     float* lv = reinterpret_cast<float*>(smem);                    // [256 rows][4 wave cols]
@@ -986,6 +1029,15 @@ __global__ __launch_bounds__(256) void gemm_argmax_reduce_kernel(const float* __
     if (ov > v || (ov == v && oc < c)) { v = ov; c = oc; }
   }
   if (lane == 0) out[row] = c == 0x7fffffff ? 0 : c;   // all-NaN row: token 0
+}
+
+// out[k][i] = the noise bits of column n0 + i under key k (sample_noise.h):
+// lets a test compare the device generator with the numpy twin directly
+__global__ __launch_bounds__(256) void sample_bits_kernel(const uint32_t* __restrict__ keys, uint32_t n0, int count,
+                                                          uint32_t* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int k = blockIdx.y;
+  if (i < count) out[(int64_t)k * count + i] = sn_bits(keys[2 * k], keys[2 * k + 1], n0 + (uint32_t)i);
 }
 
 #undef GM_STAGE

@@ -372,6 +372,38 @@ static void gemm_argmax(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr_t
   check_launch();
 }
 
+// LM head + per-row temperature sampling: out[m] = argmax_n (A[m] . W[n] * inv_temp[m] + G(key[m], n)),
+// the Gumbel noise of sample_noise.h, in the GEMM epilogue (GM_EPI_SAMPLE);
+// inv_temp[m] == 0: row m is greedy (gemm_argmax's result).  inv_temp
+// [rows_padded] fp32 and key [rows_padded][2] uint32 hold whole 256-row tiles.
+static void gemm_sample(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr_t inv_temp, uintptr_t key,
+                        int rows_padded, uintptr_t pv, uintptr_t pi, uintptr_t out, uintptr_t stream) {
+  require(M > 0 && N % GM_BN == 0 && K % (2 * GM_BK) == 0, "gemm_sample: M > 0, N % 256, K % 128");
+  require((int64_t)M * K < (1LL << 30) && (int64_t)N * K < (1LL << 30), "gemm_sample: operand > 2 GiB");
+  require(a % 16 == 0 && w % 16 == 0 && pv % 4 == 0 && pi % 4 == 0 && out % 4 == 0, "gemm_sample: alignment");
+  require(inv_temp != 0 && key != 0 && inv_temp % 16 == 0 && key % 16 == 0,
+          "gemm_sample: inv_temp / key must be 16-byte aligned");
+  require(rows_padded >= (M + GM_BM - 1) / GM_BM * GM_BM, "gemm_sample: inv_temp / key must hold whole 256-row tiles");
+  GmSide side{P<float>(pv), P<int32_t>(pi)};
+  side.inv_temp = P<const float>(inv_temp);
+  side.key = P<const uint32_t>(key);
+  launch_gemm<GM_EPI_SAMPLE>(P<const uint16_t>(a), P<const uint16_t>(w), nullptr, M, N, K, S(stream), GM_GROUP_M,
+                             nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, side);
+  hipLaunchKernelGGL(gemm_argmax_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, S(stream), P<const float>(pv),
+                     P<const int32_t>(pi), M, N / GM_BN, P<int32_t>(out));
+  check_launch();
+}
+
+// out[k][i] = noise bits of column n0 + i under keys[k] = (k0, k1): the device generator, for tests
+static void sample_bits(uintptr_t keys, int n_keys, uint32_t n0, int count, uintptr_t out, uintptr_t stream) {
+  require(n_keys >= 0 && n_keys <= 65535 && count >= 0, "sample_bits: bad counts");
+  require(keys % 4 == 0 && out % 4 == 0, "sample_bits: alignment");
+  if (n_keys == 0 || count == 0) return;
+  hipLaunchKernelGGL(sample_bits_kernel, dim3((count + 255) / 256, n_keys), dim3(256), 0, S(stream),
+                     P<const uint32_t>(keys), n0, count, P<uint32_t>(out));
+  check_launch();
+}
+
 static void row_rms(uintptr_t x, uintptr_t r, int T, int D, float eps, uintptr_t stream) {
   require(T >= 0 && D > 0 && D % 512 == 0, "row_rms expects D % 512 == 0");
   require(x % 16 == 0 && r % 4 == 0, "row_rms: misaligned pointers");
@@ -655,6 +687,11 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("rs") = 0, py::arg("split_full") = 0, py::arg("split_ws") = 0, py::arg("split_cnt") = 0,
         py::arg("group_m") = GM_GROUP_M);
   m.def("gemm_argmax", &gemm_argmax);
+  m.def("gemm_sample", &gemm_sample, py::arg("a"), py::arg("w"), py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("inv_temp"), py::arg("key"), py::arg("rows_padded"), py::arg("pv"), py::arg("pi"), py::arg("out"),
+        py::arg("stream"));
+  m.def("sample_bits", &sample_bits, py::arg("keys"), py::arg("n_keys"), py::arg("n0"), py::arg("count"),
+        py::arg("out"), py::arg("stream"));
   m.def("row_rms", &row_rms);
   m.attr("GEMM_EPI_STORE") = (int)GM_EPI_STORE;
   m.attr("GEMM_EPI_SWIGLU") = (int)GM_EPI_SWIGLU;

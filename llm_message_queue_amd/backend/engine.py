@@ -30,6 +30,7 @@ layers of the stub, never skipped.
 from __future__ import annotations
 
 import collections
+import math
 import time
 from dataclasses import dataclass
 from typing import Deque, Dict, List, Optional, Sequence
@@ -38,6 +39,8 @@ import numpy as np
 import torch
 
 from ..models.llama_stub import LlamaConfig, LlamaStub
+from ..ops.gemm import row_scale_len
+from ..ops.sampling import inv_temperature, row_keys
 
 
 @dataclass
@@ -72,6 +75,11 @@ class Request:
     # go back with the completion record even when ``conv`` is -1 (no KV
     # residency), so the origin's dialog history holds the real ids
     dialog: bool = False
+    # sampling: 0 = greedy, else tokens are drawn from softmax(logits /
+    # temperature) with noise that is a pure function of (seed, index of the
+    # generated token, vocabulary column) -- ``ops.sampling``; no top-k / top-p
+    temperature: float = 0.0
+    seed: int = 0
 
 
 @dataclass
@@ -275,6 +283,9 @@ class BackendEngine:
         self.s_tier = np.zeros(n_all, dtype=np.int64)
         self.s_micro = np.zeros(n_all, dtype=bool)
         self.s_micro[slots:] = True
+        self.s_temp = np.zeros(n_all, dtype=np.float32)     # sampling temperature (0: greedy)
+        self.s_seed = np.zeros(n_all, dtype=np.uint64)      # sampling seed
+        self.sampled_steps = 0                              # forwards that ended in the sampling head
         # host copy of every generated token id, per slot (written when the
         # step that sampled it is reaped; steps of one pool are reaped in
         # launch order, so a slot's next request never overwrites a row
@@ -312,7 +323,9 @@ class BackendEngine:
         # read it has finished: launch keeps <= max_inflight steps queued, so
         # step k reuses step k - ring's buffer only once that one was reaped)
         ring = max(2, self.max_inflight)
-        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 2 * slots + 64)) for _ in range(ring)]
+        # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles)
+        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 2 * slots + 64 + 3 * row_scale_len(slots) + 4))
+                      for _ in range(ring)]
         # sampled token ids copied back behind each forward (read at reap)
         self._out_pins = [self._alloc_pin(4 * self.n_all).view(torch.int32) for _ in range(ring)]
         # realtime micro-forwards: their own queue, staging, token gather source
@@ -331,7 +344,8 @@ class BackendEngine:
             # gather rows (<= 3T) and ~one 1-token tile per row (4T) -- sized
             # so it never grows (a grown pinned buffer frees the old one
             # behind the copies still queued from it)
-            self._pins_m = [self._alloc_pin(4 * (11 * self.micro_budget + 2 * self.micro_slots + 64))
+            self._pins_m = [self._alloc_pin(4 * (11 * self.micro_budget + 2 * self.micro_slots + 64
+                                                 + 3 * row_scale_len(self.micro_slots) + 4))
                             for _ in range(mr)]
             self._out_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32) for _ in range(mr)]
         # segment-tiled MFMA attention on the HIP path (per-token otherwise)
@@ -580,6 +594,12 @@ class BackendEngine:
             self.s_pref[s] = base
             self.s_gen[s] = 0
             self.s_gmax[s] = r.gen_tokens
+            if r.temperature:
+                t = float(r.temperature)
+                self.s_temp[s] = t if (t > 0 and math.isfinite(t)) else 0.0
+                self.s_seed[s] = int(r.seed) & 0xFFFFFFFFFFFFFFFF
+            else:
+                self.s_temp[s] = 0.0
             # prefill order key: realtime-lane tiers sort before everything else
             self.s_seq[s] = self._admit_seq - (1 << 48 if 0 <= r.tier < self.fast_tiers else 0)
             self._admit_seq += 1
@@ -1008,20 +1028,36 @@ class BackendEngine:
             return False
         dev = self.device
         S, D, NT = len(samp), len(dec_rows), len(tiles)
-        if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None:
+        # a step with a sampling row (temperature > 0) ends in the sampling
+        # head; an all-greedy step is the call (and the staging buffer) it
+        # always was.  The captured micro graphs hold the greedy head: a
+        # decode micro-forward with a sampling row takes the eager path.
+        temp = self.s_temp[samp_slots]
+        sampling = bool(S) and bool((temp > 0).any())
+        if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling:
             Tb = next((b for b in self.MICRO_GRAPH_BUCKETS if b >= T and b in self._mg), 0)
             if Tb:
                 return self._launch_micro_graph(Tb, t0, t_mono, pos, slot, samp_slots, dec_src)
         o_dec = 3 * T + S
         o_til = o_dec + 2 * D
-        buf = np.empty(o_til + 4 * NT, dtype=np.int32)
+        # sampling rows: 1 / T (float32 bits) and the row keys of the S
+        # sampled rows behind the tiles, both whole 256-row tiles long and
+        # 16-byte aligned on the device (the epilogue's vector loads)
+        o_smp = (o_til + 4 * NT + 3) & ~3 if sampling else o_til + 4 * NT
+        Sp = row_scale_len(S) if sampling else 0
+        buf = np.empty(o_smp + 3 * Sp, dtype=np.int32)
+        if sampling:
+            buf[o_til + 4 * NT:] = 0
+            buf[o_smp:o_smp + S] = inv_temperature(temp).view(np.int32)
+            buf[o_smp + Sp:o_smp + Sp + 2 * S] = \
+                row_keys(self.s_seed[samp_slots], self.s_gen[samp_slots]).view(np.int32).reshape(-1)
         buf[:T] = toks
         buf[T:2 * T] = pos
         buf[2 * T:3 * T] = slot
         buf[3 * T:o_dec] = samp
         buf[o_dec:o_dec + D] = dec_rows
         buf[o_dec + D:o_til] = dec_src
-        buf[o_til:] = tiles.reshape(-1)
+        buf[o_til:o_til + 4 * NT] = tiles.reshape(-1)
         nbytes = buf.nbytes
         sid = self.micro_id if micro else self.step_id
         pins, outs = (self._pins_m, self._out_pins_m) if micro else (self._pins, self._out_pins)
@@ -1043,17 +1079,23 @@ class BackendEngine:
                 rows = d[o_dec:o_dec + D].long()
                 src = d[o_dec + D:o_til].long()
                 tok_d.index_copy_(0, rows, prev.index_select(0, src).long())
-            til = d[o_til:].view(NT, 4) if self.use_tiles else None
+            til = d[o_til:o_til + 4 * NT].view(NT, 4) if self.use_tiles else None
+            skw = {}
+            if sampling:
+                skw = {"inv_temp": d[o_smp:o_smp + Sp].view(torch.float32),
+                       "keys": d[o_smp + Sp:o_smp + 3 * Sp].view(Sp, 2)}
+                self.sampled_steps += 1
             ev0 = self._start_event()
             te = time.perf_counter_ns()
             if micro and self.micro_cus and self.micro_gemm == "rocblas":
                 with _blas("cublas"):
                     out = self.model.forward(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til,
-                                             n_dec=D)
+                                             n_dec=D, **skw)
             else:
                 out = self.model.forward(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til,
                                          n_dec=D,
-                                         **({"small_cus": self.micro_cus} if micro and self.micro_cus else {}))
+                                         **({"small_cus": self.micro_cus} if micro and self.micro_cus else {}),
+                                         **skw)
             self.host_ns[2] += time.perf_counter_ns() - te
             if not micro:
                 self._census(T)

@@ -26,8 +26,9 @@ K_CANCEL = 7        # [kind, handle lo/hi, origin]: origin -> the GPU running it
 K_HIST = 8
 # completion records (K_DONE) carry the turn's generated token ids in the
 # payload columns, their count in col 10 (dialog turns: the origin's history)
-DESC_HDR = 17       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/hi, gen, plen, flags, conv lo/hi,
-#                    dialog history length, decision - enq (us), processing timeout (ms)];
+DESC_HDR = 20       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/hi, gen, plen, flags, conv lo/hi,
+#                    dialog history length, decision - enq (us), processing timeout (ms),
+#                    sampling temperature (float32 bits), sampling seed lo/hi];
 #                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN
 KV_MIGRATE = 1 << 8     # descriptor flag: hold the turn until its KV arrives from the home GPU
 DIALOG_TURN = 1 << 9    # descriptor flag: a conversation turn -- its generated ids go back with K_DONE

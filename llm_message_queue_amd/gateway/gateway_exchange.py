@@ -341,6 +341,8 @@ class ExchangeMixin:
         v = np.empty((n, 4), dtype=np.int64)      # handle, arrival, enq, conversation key
         small = np.zeros((n, 6), dtype=np.int64)  # tier, plen, flags, hist len, decision - enq (us)
         kv = self.kv_residency
+        temp = np.zeros(n, dtype=np.float32)      # sampling temperature (float32 bits in col 17), seed
+        seed = np.zeros(n, dtype=np.int64)
         prompts = []
         ctx = []
         for k, m in enumerate(msgs):
@@ -363,6 +365,7 @@ class ExchangeMixin:
             small[k, 4] = min(0x7FFFFFFF, max(0, (m.popped_ns - m.enqueued_at) // 1000)) \
                 if (m.popped_ns and m.enqueued_at) else 0
             small[k, 5] = min(0x7FFFFFFF, self._timeout_ns(m) // 1_000_000)
+            temp[k], seed[k] = self._sampling(m)
         buf[:, 0] = K_DISPATCH
         _put64(buf, 1, v[:, 0])
         buf[:, 3] = origin
@@ -376,6 +379,8 @@ class ExchangeMixin:
         buf[:, 14] = small[:, 3]
         buf[:, 15] = small[:, 4]
         buf[:, 16] = small[:, 5]
+        buf[:, 17] = temp.view(np.int32)
+        _put64(buf, 18, seed)
         for k, p in enumerate(prompts):
             if len(p):
                 buf[k, DESC_HDR:DESC_HDR + len(p)] = p.view(np.int32)
@@ -457,6 +462,8 @@ class ExchangeMixin:
         """Requests for K_DISPATCH descriptor rows (another router's
         messages placed on this GPU)."""
         handle, arrival, enq, ck = _get64(rows, 1), _get64(rows, 5), _get64(rows, 7), _get64(rows, 12)
+        temps = np.ascontiguousarray(rows[:, 17]).view(np.float32).tolist()
+        seeds = _get64(rows, 18).tolist()
         dec = enq + rows[:, 15].astype(np.int64) * 1000
         out = []
         mask = (1 << HIST_LEN_BITS) - 1
@@ -474,7 +481,8 @@ class ExchangeMixin:
                                gen_tokens=gen, tier=tier, meta=(origin, h, tier, a, e, d), conv=c,
                                history=np.zeros(hl, dtype=np.int32) if hl > 0 else None,
                                prefix=np.zeros(pl, dtype=np.int32) if pl > 0 else None,
-                               timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN)))
+                               timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN),
+                               temperature=temps[k], seed=seeds[k]))
         return out
 
     def _remote_done_rows(self, rows: np.ndarray) -> None:

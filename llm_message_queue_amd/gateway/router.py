@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..backend.engine import BackendEngine, Request
-from ..models.message import Message, MessageStatus, priority_name
+from ..models.message import Message, MessageStatus, SamplingParseError, priority_name, sampling_from_metadata
 from ..parallel import planner
 from ..parallel.comm import Comm, SoloComm
 from ..queue.core import QueueError
@@ -447,8 +447,28 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             if len(prompt) else np.zeros(1, dtype=np.int32)
         ck = conv_key(m.conversation_id) if self.kv_residency else -1
         hist, pre = self._dialog_context(m)
+        temp, seed = self._sampling(m)
         return Request(req_id=m.handle, prompt=p, gen_tokens=self.gen_tokens, tier=tier, meta=m, conv=ck,
-                       history=hist, prefix=pre, timeout_ns=self._timeout_ns(m))
+                       history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed)
+
+    @staticmethod
+    def _sampling(m: Message) -> Tuple[float, int]:
+        """The message's effective ``(temperature, seed)``
+        (``metadata.sampling``), lenient: this path also serves messages
+        no route validated (the native ingress), so a bad value falls back
+        to greedy and is reported in ``metadata["sampling_error"]``.  A
+        message that asked for sampling gets the effective values written
+        back, so a client can replay it."""
+        md = m.metadata
+        if not md or "sampling" not in md:
+            return 0.0, 0                         # greedy (the default traffic): the seed is never read
+        try:
+            temp, seed = sampling_from_metadata(md, m.id)
+        except SamplingParseError as e:
+            md["sampling_error"] = str(e)
+            temp, seed = 0.0, sampling_from_metadata(None, m.id)[1]
+        md["sampling"] = {"temperature": temp, "seed": seed}
+        return temp, seed
 
     def _timeout_ns(self, m: Message) -> int:
         return int(m.timeout) if (self.inflight_timeout and m.timeout and m.timeout > 0) else 0

@@ -200,9 +200,13 @@ class LlamaStub:
     @torch.no_grad()
     def forward(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 sample_idx: torch.Tensor, tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
-                small_cus: int = 0) -> torch.Tensor:
+                small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
+                keys: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step over T tokens; returns greedy next-token ids for the rows
-        in ``sample_idx`` (the last token of each request's chunk).
+        in ``sample_idx`` (the last token of each request's chunk).  With
+        ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
+        (``ops.sampling.row_keys``) the head samples instead
+        (``ops.sample_head``: temperature sampling by Gumbel-max).
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -217,6 +221,9 @@ class LlamaStub:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec,
                               small_cus=small_cus).index_select(0, sample_idx)
         hand = small_cus or not self.library_gemm
+        if inv_temp is not None and keys is not None:
+            return self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
+                                        min_rows=1 if hand else 256)
         return self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
 
     @torch.no_grad()

@@ -309,6 +309,46 @@ def new_message(conversation_id: str, user_id: str, content: str, priority: int)
                    created_at=t, updated_at=t, metadata={})
 
 
+# --------------------------------------------------------------------------- sampling parameters
+TEMPERATURE_MIN, TEMPERATURE_MAX = 0.05, 2.0
+
+
+class SamplingParseError(ValueError):
+    pass
+
+
+def default_seed(message_id: str) -> int:
+    """63-bit seed of a message that names none: a hash of its id, so every
+    retry / replay of the message draws the same tokens."""
+    import hashlib
+    return int.from_bytes(hashlib.blake2b((message_id or "").encode(), digest_size=8).digest(), "little") >> 1
+
+
+def sampling_from_metadata(md: Any, message_id: str = "") -> tuple:
+    """``(temperature, seed)`` of a message's ``metadata.sampling`` object.
+
+    ``temperature``: 0 (greedy, the default) or a number in [0.05, 2.0].
+    ``seed``: an integer in [0, 2^63); without one, ``default_seed(message_id)``.
+    There is no top-k / top-p.  Raises ``SamplingParseError`` on anything else."""
+    sp = md.get("sampling") if isinstance(md, dict) else None
+    if sp is None:
+        return 0.0, default_seed(message_id)
+    if not isinstance(sp, dict):
+        raise SamplingParseError("sampling must be an object")
+    t = sp.get("temperature", 0.0)
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t):
+        raise SamplingParseError("sampling.temperature must be a number")
+    t = float(t)
+    if t != 0.0 and not (TEMPERATURE_MIN <= t <= TEMPERATURE_MAX):
+        raise SamplingParseError(f"sampling.temperature must be 0 or in [{TEMPERATURE_MIN}, {TEMPERATURE_MAX}]")
+    seed = sp.get("seed")
+    if seed is None:
+        seed = default_seed(message_id)
+    elif isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < (1 << 63)):
+        raise SamplingParseError("sampling.seed must be an integer in [0, 2^63)")
+    return t, int(seed)
+
+
 # --------------------------------------------------------------------------- conversation
 class Conversation:
     """`message.go:93-109`, plus the summary state produced by the

@@ -421,3 +421,58 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor = None) -
                                          y.data_ptr(), stream)
     return y
 
+
+def lm_head_sample(x: torch.Tensor, w: torch.Tensor, inv_temp: torch.Tensor, keys: torch.Tensor,
+                   out: torch.Tensor = None) -> torch.Tensor:
+    """Per-row temperature sampling ``argmax_n (x . w[n] * inv_temp + G(key,
+    n))`` -> int32 [M] in the GEMM epilogue (``lm_head_argmax`` with the
+    Gumbel noise of ``ops.sampling`` / ``sample_noise.h`` added to the scaled
+    accumulators): an exact draw from ``softmax(logits / T)`` with no logits
+    tensor and no softmax pass.  ``inv_temp`` float32 [>= M] (0: the row is
+    greedy and equals ``lm_head_argmax``'s), ``keys`` 32-bit [>= M][2] =
+    ``ops.sampling.row_keys``.  The kernel reads whole 256-row tiles of both:
+    pass them ``row_scale_len(M)`` rows long (rows past M zero) or they are
+    padded here.  Shares ``lm_head_argmax``'s scratch."""
+    _check(x, "x")
+    _check(w, "w")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or not supported(M, N, K):
+        raise ValueError(f"lm_head_sample: unsupported shape M={M} N={N} K={K}")
+    if inv_temp.dtype != torch.float32 or inv_temp.dim() != 1 or inv_temp.numel() < M or inv_temp.device != x.device:
+        raise ValueError("lm_head_sample: inv_temp must be float32 [>= M] on x's device")
+    if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 2 or keys.shape[1] != 2 \
+            or keys.shape[0] < M or keys.device != x.device:
+        raise ValueError("lm_head_sample: keys must be 32-bit [>= M][2] on x's device")
+    Mp = row_scale_len(M)
+    if inv_temp.numel() < Mp or not inv_temp.is_contiguous() or inv_temp.data_ptr() % 16:
+        inv_temp = torch.nn.functional.pad(inv_temp[:M], (0, Mp - M))
+    if keys.shape[0] < Mp or not keys.is_contiguous() or keys.data_ptr() % 16:
+        keys = torch.nn.functional.pad(keys[:M].view(torch.int32), (0, 0, 0, Mp - M))
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    key = (x.device.type, x.device.index, stream)
+    need = M * (N // TILE_N)
+    ws = _ARGMAX_WS.get(key)
+    if ws is None or ws[0].numel() < need:
+        n = max(need, 2 * ws[0].numel() if ws is not None else 0)
+        ws = _ARGMAX_WS[key] = (torch.empty(n, dtype=torch.float32, device=x.device),
+                                torch.empty(n, dtype=torch.int32, device=x.device))
+    y = out if out is not None else torch.empty(M, dtype=torch.int32, device=x.device)
+    if y.dtype != torch.int32 or y.numel() < M or not y.is_contiguous():
+        raise ValueError("lm_head_sample: out must be contiguous int32 [M]")
+    _native.require_hipops().gemm_sample(x.data_ptr(), w.data_ptr(), M, N, K, inv_temp.data_ptr(), keys.data_ptr(),
+                                         Mp, ws[0].data_ptr(), ws[1].data_ptr(), y.data_ptr(), stream)
+    return y
+
+
+def sample_bits(keys: torch.Tensor, n0: int, count: int) -> torch.Tensor:
+    """The device noise generator's bits (int32 [n_keys][count], the uint32
+    bit patterns) of columns ``n0 .. n0 + count`` under ``keys`` [n][2]."""
+    if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 2 or keys.shape[1] != 2 \
+            or not keys.is_contiguous():
+        raise ValueError("sample_bits: keys must be contiguous 32-bit [n][2]")
+    out = torch.empty((keys.shape[0], count), dtype=torch.int32, device=keys.device)
+    _native.require_hipops().sample_bits(keys.data_ptr(), keys.shape[0], int(n0) & 0xFFFFFFFF, int(count),
+                                         out.data_ptr(), torch.cuda.current_stream(keys.device).cuda_stream)
+    return out
+

@@ -92,6 +92,25 @@ class HipOps:
             return G.lm_head_argmax(x, w)
         return torch.argmax(torch.nn.functional.linear(x, w), dim=-1).to(torch.int32)
 
+    def sample_head(self, x, w, inv_temp, keys, fused: bool = True, min_rows: int = 256):
+        """Tokens of the LM head under per-row temperature sampling (int32
+        [M]; ``ops.gemm.lm_head_sample``): the hand-written GEMM with the
+        sampling epilogue from ``min_rows`` rows (no logits tensor), else
+        the same scores (fp32 logits * inv_temp + the contract's noise, from
+        the device generator) over a logits tensor."""
+        from . import gemm as G
+        M = x.shape[0]
+        if fused and M >= min_rows and G.supported(M, w.shape[0], x.shape[1]):
+            return G.lm_head_sample(x, w, inv_temp, keys)
+        from .sampling import SERIES_BELOW
+        lg = torch.nn.functional.linear(x, w).float()
+        m = G.sample_bits(keys[:M].contiguous(), 0, w.shape[0]).to(torch.int64) & 0xFFFFFFFF
+        v = (m.double() + 0.5) * 2.0 ** -32
+        e = torch.where(v < SERIES_BELOW, v * (1.0 + v * (0.5 + v / 3.0)), -torch.log1p(-v.clamp(min=SERIES_BELOW)))
+        it = inv_temp[:M, None]
+        sc = torch.where(it != 0, lg.double() * it.double() - torch.log(e), lg.double())
+        return torch.argmax(sc, dim=-1).to(torch.int32)
+
     def mlp_up(self, x: torch.Tensor, w_gu: torch.Tensor, fused: bool, min_fused_tokens: int) -> torch.Tensor:
         """silu(x·Wgᵀ) * (x·Wuᵀ).  ``fused``: ``w_gu`` is in swiglu order and
         steps of >= ``min_fused_tokens`` rows run the hand-written GEMM with
@@ -207,6 +226,18 @@ class RefOps:
 
     def greedy_head(self, x, w, fused: bool = True, min_rows: int = 256):
         return torch.argmax(torch.nn.functional.linear(x, w), dim=-1).to(torch.int32)
+
+    def sample_head(self, x, w, inv_temp, keys, fused: bool = True, min_rows: int = 256):
+        """Reference of ``HipOps.sample_head`` (the CPU path and the tests'
+        oracle): fp32 logits, the numpy twin's noise, float64 scores."""
+        from .sampling import sample_reference
+        M = x.shape[0]
+        lg = (x.float() @ w.float().t()).cpu().numpy()
+        kk = keys[:M].cpu().contiguous().view(torch.int32).numpy().view("uint32")
+        it = inv_temp[:M]
+        picks = torch.from_numpy(sample_reference(lg, it.cpu().numpy(), kk)).to(x.device)
+        # a greedy row is exactly this class's greedy_head (bf16 logits)
+        return torch.where(it != 0, picks, self.greedy_head(x, w, fused, min_rows))
 
     def mlp_up(self, x, w_gu, fused: bool, min_fused_tokens: int):
         """Reference of ``HipOps.mlp_up`` (``w_gu`` in swiglu order if fused)."""

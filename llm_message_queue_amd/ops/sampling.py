@@ -1,0 +1,101 @@
+"""Host twin of the LM head's sampling noise (``csrc/kernels/sample_noise.h``
+holds the contract and the device code).
+
+Temperature sampling is ``argmax_n(logit_n / T + G_n)`` with i.i.d. standard
+Gumbel ``G_n`` -- an exact draw from ``softmax(logits / T)``.  ``G_n`` is a
+pure function of (request seed, index of the generated token, vocabulary
+column), so a request's tokens are reproducible whatever step, row, batch or
+GPU computed them.  The integer part (row keys, bits) equals the device's
+bit for bit; the Gumbel values are the same two-branch formula in float64.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+GOLDEN = 0x9E3779B97F4A7C15
+SERIES_BELOW = 2.0 ** -12            # E = v + v*v/2 + v*v*v/3 below, -log(1 - v) from here on
+
+
+def fmix32(h) -> np.ndarray:
+    """The murmur3 finaliser over uint32 arrays."""
+    h = np.asarray(h, dtype=np.uint32).copy()
+    h ^= h >> np.uint32(16)
+    h *= np.uint32(0x85EBCA6B)
+    h ^= h >> np.uint32(13)
+    h *= np.uint32(0xC2B2AE35)
+    h ^= h >> np.uint32(16)
+    return h
+
+
+def splitmix64(x) -> np.ndarray:
+    x = np.asarray(x, dtype=np.uint64) + np.uint64(GOLDEN)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def row_keys(seed, gidx) -> np.ndarray:
+    """uint32 [n][2] = (k0, k1) of generated token ``gidx`` (its index within
+    the request) under ``seed``; both broadcast."""
+    with np.errstate(over="ignore"):
+        s = np.asarray(seed, dtype=np.uint64)
+        g = np.asarray(gidx, dtype=np.int64).astype(np.uint64)
+        z = np.atleast_1d(splitmix64(s + np.uint64(GOLDEN) * (g + np.uint64(1))))
+    out = np.empty((len(z), 2), dtype=np.uint32)
+    out[:, 0] = (z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    out[:, 1] = (z >> np.uint64(32)).astype(np.uint32)
+    return out
+
+
+def noise_bits(keys, cols) -> np.ndarray:
+    """uint32 [n_keys][n_cols]: ``m = fmix32(fmix32(n ^ k0) + k1)``."""
+    keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
+    n = np.asarray(cols, dtype=np.uint32).reshape(1, -1)
+    with np.errstate(over="ignore"):
+        return fmix32(fmix32(n ^ keys[:, 0:1]) + keys[:, 1:2])
+
+
+def exponential_series(v) -> np.ndarray:
+    v = np.asarray(v, dtype=np.float64)
+    return v * (1.0 + v * (0.5 + v / 3.0))
+
+
+def exponential_log(v) -> np.ndarray:
+    return -np.log(1.0 - np.asarray(v, dtype=np.float64))
+
+
+def gumbel_from_bits(m) -> np.ndarray:
+    """float64 standard Gumbel of the bits ``m``: ``v = (m + 0.5) * 2^-32``,
+    ``E = -log1p(-v)`` by the contract's two branches, ``G = -log(E)``."""
+    v = (np.asarray(m, dtype=np.uint32).astype(np.float64) + 0.5) * 2.0 ** -32
+    small = v < SERIES_BELOW
+    e = np.where(small, exponential_series(v), exponential_log(np.where(small, 0.5, v)))
+    return -np.log(e)
+
+
+def gumbel(keys, cols) -> np.ndarray:
+    return gumbel_from_bits(noise_bits(keys, cols))
+
+
+def inv_temperature(temperature) -> np.ndarray:
+    """float32 1 / T, 0 for a greedy row (T <= 0)."""
+    t = np.asarray(temperature, dtype=np.float64)
+    return np.where(t > 0, 1.0 / np.where(t > 0, t, 1.0), 0.0).astype(np.float32)
+
+
+def sample_reference(logits, inv_temp, keys) -> np.ndarray:
+    """The reference sampler: int32 [M] picks over ``logits`` [M][V]
+    (float64 scores; a row with ``inv_temp == 0`` is the plain argmax, ties
+    to the lower column)."""
+    lg = np.asarray(logits, dtype=np.float64)
+    it = np.asarray(inv_temp, dtype=np.float32).astype(np.float64).reshape(-1)
+    keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
+    M, V = lg.shape
+    out = np.empty(M, dtype=np.int32)
+    cols = np.arange(V, dtype=np.uint32)
+    for i in range(0, M, 64):                       # (noise in row chunks: [64][V] float64)
+        j = min(M, i + 64)
+        g = gumbel(keys[i:j], cols)
+        sc = np.where(it[i:j, None] != 0, lg[i:j] * it[i:j, None] + g, lg[i:j])
+        out[i:j] = sc.argmax(axis=1)
+    return out

@@ -1,21 +1,27 @@
 // Where does the gate/up GEMM's time go on a power-bound MI355X?  A/B of the
-// production 8-wave kernel (SCHED 2) against diagnostic builds of the same
-// template that drop one kind of work from the steady-state K loop while
-// keeping every MFMA (numerics are WRONG for 5-7; timing only):
+// production 8-wave kernel against the diagnostic builds of the same template
+// (the GM_DIAG_* enum of gemm_kernels.h) that drop one kind of work from the
+// steady-state K loop while keeping every MFMA (numerics are WRONG for all
+// but 0 and 4; timing only).  The "sched" field of the output is the
+// GM_DIAG_* value:
 //
-//   2  production
-//   5  A fragment reads of phases 3 / 7 skipped: one third fewer LDS read
-//      bytes -- what a 128 x 128 wave tile (4 waves) would read per MFMA
-//   6  no fragment reads in the loop (MFMA + staging DMA only)
-//   7  no staging DMA in the loop (MFMA + LDS fragment reads only)
-//   8 / 9  2 / 7 with entry and exit clock stamps: the in-kernel shader
-//      clock, unprofiled
-//   10 every block stages tile (0, 0)'s panels: staging served from L2
-//      (what better L2 reuse could be worth at most)
+//   0  GM_DIAG_NONE: production
+//   1  GM_DIAG_SKIP_A2: A fragment reads of phases 3 / 7 skipped: one third
+//      fewer LDS read bytes -- what a 128 x 128 wave tile (4 waves) would read
+//      per MFMA
+//   2  GM_DIAG_NO_LDS_READ: no fragment reads in the loop (MFMA + staging DMA only)
+//   3  GM_DIAG_NO_DMA: no staging DMA in the loop (MFMA + LDS fragment reads only)
+//   4 / 5  GM_DIAG_CLOCK / GM_DIAG_CLOCK_NO_DMA: 0 / 3 with entry and exit
+//      clock stamps: the in-kernel shader clock, unprofiled
+//   6  GM_DIAG_L2_PANELS: every block stages tile (0, 0)'s panels: staging
+//      served from L2 (what better L2 reuse could be worth at most)
 //
-// If 5 or 6 run much faster, LDS read traffic (its issue time or its energy
+// (Records made before the builds had names, profiles/r4_gemm_energy_diag*,
+// carry 2 / 5 / 6 / 7 / 8 / 9 / 10 for the same seven, in this order.)
+//
+// If 1 or 2 run much faster, LDS read traffic (its issue time or its energy
 // under the power cap) limits the kernel and a bigger wave tile pays; if only
-// 7 does, it is the L2 / HBM side.  Interleaved rounds in one process,
+// 3 does, it is the L2 / HBM side.  Interleaved rounds in one process,
 // random operands (cdna_hip_programming.md §5.4 rules 24 / 25).
 //
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I csrc bench/gemm_energy_diag.hip -o /tmp/gemm_energy_diag
@@ -55,17 +61,17 @@ __global__ void fill_bf16(uint16_t* p, size_t n, uint32_t seed, float scale) {
   }
 }
 
-template <int SCHED>
+template <int DIAG>
 static void launch(const uint16_t* a, const uint16_t* w, uint16_t* c, int M, int N, int K,
                    uint64_t* dbg = nullptr) {
   static bool attr = false;
   if (!attr) {
-    CK(hipFuncSetAttribute((const void*)gemm_bf16_kernel<GM_EPI_SWIGLU, true, SCHED>,
+    CK(hipFuncSetAttribute((const void*)gemm_bf16_kernel<GM_EPI_SWIGLU, DIAG>,
                            hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES));
     attr = true;
   }
   const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
-  hipLaunchKernelGGL((gemm_bf16_kernel<GM_EPI_SWIGLU, true, SCHED>), dim3(tiles), dim3(GM_THREADS), GM_LDS_BYTES, 0,
+  hipLaunchKernelGGL((gemm_bf16_kernel<GM_EPI_SWIGLU, DIAG>), dim3(tiles), dim3(GM_THREADS), GM_LDS_BYTES, 0,
                      a, w, c, M, N, K, GM_GROUP_M, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr},
                      GmSide{reinterpret_cast<float*>(dbg), nullptr});
 }
@@ -90,14 +96,14 @@ int main(int argc, char** argv) {
   CK(hipDeviceSynchronize());
 
   const int NV = 5;
-  const int scheds[NV] = {2, 5, 6, 7, 10};
+  const int scheds[NV] = {GM_DIAG_NONE, GM_DIAG_SKIP_A2, GM_DIAG_NO_LDS_READ, GM_DIAG_NO_DMA, GM_DIAG_L2_PANELS};
   auto run = [&](int s) {
     switch (s) {
-      case 2: launch<2>(a, w, c, M, N, K); break;
-      case 5: launch<5>(a, w, c, M, N, K); break;
-      case 6: launch<6>(a, w, c, M, N, K); break;
-      case 7: launch<7>(a, w, c, M, N, K); break;
-      default: launch<10>(a, w, c, M, N, K); break;
+      case GM_DIAG_NONE: launch<GM_DIAG_NONE>(a, w, c, M, N, K); break;
+      case GM_DIAG_SKIP_A2: launch<GM_DIAG_SKIP_A2>(a, w, c, M, N, K); break;
+      case GM_DIAG_NO_LDS_READ: launch<GM_DIAG_NO_LDS_READ>(a, w, c, M, N, K); break;
+      case GM_DIAG_NO_DMA: launch<GM_DIAG_NO_DMA>(a, w, c, M, N, K); break;
+      default: launch<GM_DIAG_L2_PANELS>(a, w, c, M, N, K); break;
     }
   };
   // ~2 s of back-to-back launches first so the clock has settled (DVFS give-back)
@@ -105,12 +111,12 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   for (int i = 0; warm_ms > 0.f && i < 3000; ++i) {
-    run(2);
+    run(GM_DIAG_NONE);
     if (i % 100 == 99) {
       CK(hipDeviceSynchronize());
       float ms = 0;
       CK(hipEventRecord(e0));
-      run(2);
+      run(GM_DIAG_NONE);
       CK(hipEventRecord(e1));
       CK(hipEventSynchronize(e1));
       CK(hipEventElapsedTime(&ms, e0, e1));
@@ -137,14 +143,17 @@ int main(int argc, char** argv) {
     printf("{\"sched\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"ms_median\": %.4f, \"ms_min\": %.4f, \"tflops\": %.1f}\n",
            scheds[v], M, N, K, med, t[v][0], flop / med / 1e9);
   }
-  // In-kernel clock, unprofiled: the production schedule (8) and the
-  // no-DMA build (9) with entry / exit stamps, each after 1 s of its own
+  // In-kernel clock, unprofiled: the production schedule (GM_DIAG_CLOCK) and the
+  // no-DMA build (GM_DIAG_CLOCK_NO_DMA) with entry / exit stamps, each after 1 s of its own
   // back-to-back launches; median over the last launch's blocks.
   const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
   uint64_t* dbg;
   CK(hipMalloc(&dbg, (size_t)tiles * 4 * sizeof(uint64_t)));
-  for (int sv : {8, 9}) {
-    auto go = [&]() { if (sv == 8) launch<8>(a, w, c, M, N, K, dbg); else launch<9>(a, w, c, M, N, K, dbg); };
+  for (int sv : {(int)GM_DIAG_CLOCK, (int)GM_DIAG_CLOCK_NO_DMA}) {
+    auto go = [&]() {
+      if (sv == GM_DIAG_CLOCK) launch<GM_DIAG_CLOCK>(a, w, c, M, N, K, dbg);
+      else launch<GM_DIAG_CLOCK_NO_DMA>(a, w, c, M, N, K, dbg);
+    };
     CK(hipEventRecord(e0));
     int n = 0;
     for (;; ++n) {

@@ -1,13 +1,22 @@
-// Hand-written gfx950 bf16 GEMM for the backend's MLP: C = A · Wᵀ with
+// Hand-written gfx950 bf16 GEMM of the backend model: C = A · Wᵀ with
 // A [M][K] and W [N][K] both K-contiguous (the layout F.linear feeds
-// hipBLASLt), fp32 accumulation on v_mfma_f32_16x16x32_bf16, and three
-// epilogues:
+// hipBLASLt), fp32 accumulation on v_mfma_f32_16x16x32_bf16.  One kernel,
+// gemm_bf16_kernel<EPI>, with nine epilogues (host entry point in hipops.hip):
 //
-//   GM_EPI_STORE   C[M][N] = A·Wᵀ                         (bf16)
-//   GM_EPI_SWIGLU  H[M][N/2] = silu(A·Wgᵀ) * (A·Wuᵀ)       (Llama gate/up)
-//   GM_EPI_RESID   C[M][N] += A·Wᵀ   (bf16 C read + written; one rounding of
-//                  the fp32 sum, as hipBLASLt's beta = 1: the o / down
-//                  projections into the residual stream)
+//   GM_EPI_STORE      C[M][N] = A·Wᵀ (bf16)                           gemm_bf16
+//   GM_EPI_SWIGLU     H[M][N/2] = silu(A·Wgᵀ) * (A·Wuᵀ)               gemm_bf16
+//   GM_EPI_ROPE       qkv projection + RoPE + K/V cache write         gemm_qkv_rope
+//   GM_EPI_ARGMAX     LM head + greedy argmax, no logits tensor       gemm_argmax
+//   GM_EPI_SAMPLE     LM head + per-row temperature sampling          gemm_sample
+//   GM_EPI_RESID      C[M][N] += A·Wᵀ, residual through registers     gemm_bf16 (A/B)
+//   GM_EPI_RESID_LDS  ... residual tile staged into LDS by DMA        gemm_bf16 (default)
+//   GM_EPI_RESID_PRE  ... its first quarter fetched at kernel start   gemm_bf16 (A/B)
+//   GM_EPI_RESID_RMS  GM_EPI_RESID_LDS + the RMSNorm row scales       gemm_residual_rms
+//
+// The residual forms read and write bf16 C with one rounding of the fp32 sum,
+// as hipBLASLt's beta = 1: the o / down projections into the residual stream.
+// STORE, SWIGLU and ROPE take optional per-row scales (the folded RMSNorm);
+// STORE, SWIGLU, ROPE and RESID_LDS can run their last tiles split-K (GmSplit).
 //
 // The SwiGLU form removes the separate silu_mul pass and the HBM round trip
 // of the [M][2F] gate/up product (profiles/r1_gemm_experiments.md): W rows are
@@ -15,6 +24,10 @@
 // output columns are 32 gate features followed by the same 32 up features,
 // i.e. every lane holds g and u of one (row, feature) in the same register
 // slot of two accumulators -- the epilogue is pure register math.
+//
+// Layout of this file: gm_tile_coords (block -> tile), gm_split_join (split-K
+// hand-over), then gemm_tile, which calls them around the main loop and ends
+// in one `if constexpr` branch per epilogue family.
 //
 // Structure (cdna_hip_programming.md §5, "the 256² 8-phase template"):
 //   * 256x256 output tile, BK = 64, 512 threads = 8 waves as 2 (M) x 4 (N),
@@ -32,14 +45,14 @@
 //   * 8 phases per 2 K-tiles: each phase reads one operand half, issues one
 //     half-tile prefetch (2 glds per lane), barrier, 16 MFMAs (one quadrant x
 //     K = 64), barrier.  The prefetch runs 3 half-tiles ahead; a counted
-//     `s_waitcnt vmcnt(6)` at phases 4 and 8 (never 0 in the steady state)
+//     `s_waitcnt vmcnt(6)` in every phase (never 0 in the steady state)
 //     retires exactly the buffer the next phase reads, and raw s_barrier is
 //     used throughout so no wait drains the DMA queue early.
 //   * XCD-aware block order: blocks that the dispatcher puts on one XCD take
 //     a contiguous run of tiles, grouped 8 M-tiles x N so concurrently
 //     running tiles share A and W panels in that XCD's L2.
 //   * M need not be a multiple of 256: A rows are clamped on load, rows >= M
-//     are not stored.  K % 64 == 0 and N % 256 == 0 are checked by the host.
+//     are not stored.  K % 128 == 0 and N % 256 == 0 are checked by the host.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -68,6 +81,21 @@ enum { GM_EPI_STORE = 0, GM_EPI_SWIGLU = 2, GM_EPI_ROPE = 3, GM_EPI_ARGMAX = 4, 
 constexpr int GM_LDS_SPARE = 32768;
 template <int EPI>
 constexpr int gm_lds_bytes() { return EPI == GM_EPI_RESID_PRE ? GM_LDS_BYTES + GM_LDS_SPARE : GM_LDS_BYTES; }
+
+// Power / energy DIAGNOSTICS of the main loop (bench/gemm_energy_diag.hip, the
+// evidence behind the README's power-cap claim; never launched by the
+// library).  Each drops one kind of work from the steady-state K loop while
+// keeping every MFMA, so all but GM_DIAG_CLOCK compute WRONG numbers:
+enum {
+  GM_DIAG_NONE = 0,          // production
+  GM_DIAG_SKIP_A2 = 1,       // no A fragment reads in phases 3 / 7: one third fewer LDS read bytes,
+                             // what a 128x128 wave tile would read
+  GM_DIAG_NO_LDS_READ = 2,   // no fragment read in the loop
+  GM_DIAG_NO_DMA = 3,        // no staging DMA in the loop (no L2 / HBM traffic in steady state)
+  GM_DIAG_CLOCK = 4,         // production + shader-clock stamps (gm_diag_stamp)
+  GM_DIAG_CLOCK_NO_DMA = 5,  // GM_DIAG_NO_DMA + the stamps
+  GM_DIAG_L2_PANELS = 6      // every block stages the panels of tile (0, 0): staging served from L2
+};
 
 // GM_EPI_ARGMAX: the LM head's greedy sampling as the epilogue -- no [M][N]
 // logits tensor.  Each tile writes, per row, the max over its 256 columns and
@@ -155,7 +183,6 @@ __device__ __forceinline__ void gm_load_row_scales(const float* __restrict__ rs,
 // accumulators (agent-scope release), the second adds them (acquire) and runs
 // the epilogue -- cdna_hip_programming.md §5 "Projection GEMM" item 2.
 #define GM_CPOL_SC1 16   // cache-policy bit: agent-scope coherent access
-typedef unsigned int gm_u32x4 __attribute__((ext_vector_type(4)));
 
 struct GmSplit {
   int full;       // tiles [0, full) run whole
@@ -164,6 +191,7 @@ struct GmSplit {
 };
 
 typedef __attribute__((address_space(3))) void* gm_lds_ptr;
+typedef gm_f32x4 gm_acc_t[2][4][2][2];             // a wave's 128 x 64 outputs: [mh][m][nh][n]
 
 // One half-tile (128 rows x 64 bf16) global -> LDS: 2 buffer_load ... lds per
 // lane.  The per-lane row/chunk offset is a fixed VGPR, the K-tile offset a
@@ -174,6 +202,8 @@ __device__ __forceinline__ void gm_stage(__amdgpu_buffer_rsrc_t rs, uint32_t v0,
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (gm_lds_ptr)(smem + dst1), 16, v1, soff, 0, 0);
 }
 
+#define GM_LGKM(N) asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory")
+#define GM_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 #define GM_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define GM_BARRIER()                  \
   do {                                \
@@ -182,52 +212,151 @@ __device__ __forceinline__ void gm_stage(__amdgpu_buffer_rsrc_t rs, uint32_t v0,
     GM_FENCE();                       \
   } while (0)
 
-// One output tile (or one K-half of a split tile): block ``bid`` of the
-// launch's block order.  gemm_bf16_kernel runs one per block, or -- PERSIST --
-// a grid of at most one block per CU walks bid, bid + gridDim.x, ...
-template <int EPI, bool STAGGER, int SCHED>
-__device__ __forceinline__ void gemm_tile(
-    uint8_t* __restrict__ smem, const uint16_t* __restrict__ A, const uint16_t* __restrict__ W,
-    uint16_t* __restrict__ C, int M, int N, int K, int group_m, const float* __restrict__ rs, const GmRope& rp,
-    const GmSplit& sp, const GmSide& am, const int bid) {
-  static_assert(EPI != GM_EPI_RESID_PRE || SCHED >= 1, "the residual prefetch is issued by the SCHED >= 1 prologue");
+// XCD-contiguous remap (bijective for any count): the dispatcher puts block
+// b of PER * count blocks on XCD b % 8; the XCDs take contiguous runs of the
+// blocks' work items, and this is where the run of b's XCD starts (b is item
+// b / 8 of that run).  PER, the blocks per tile, is a template parameter and
+// the caller adds b >> 3 because the optimiser simplifies this function
+// before it inlines it: both keep the compiler's output what it was with the
+// formula written out per caller (docs/development.md, "two-tree comparison").
+template <int PER>
+__device__ __forceinline__ int gm_xcd_run_start(int b, int count) {
+  const int n = PER * count;
+  const int xcd = b & 7, q8 = n >> 3, r8 = n & 7;
+  return xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+}
 
-  const int tiles_m = (M + GM_BM - 1) / GM_BM;
-  const int tiles_n = N / GM_BN;
-  const int nwg = tiles_m * tiles_n;
-  const int full = sp.ws ? sp.full : nwg;
-  // XCD-contiguous remap (bijective for any count) of the whole tiles, then
-  // 8-M-tile grouping; split tiles take two consecutive blocks
-  int pid, khalf = -1;
+struct GmTile {
+  int tm, tn;     // output tile
+  int pid;        // its index in the launch's tile order
+  int khalf;      // -1: the whole K; 0 / 1: this block's K-half of a split tile
+};
+
+// Block ``bid`` of the launch's block order -> its tile: the whole tiles
+// [0, full) by the XCD-contiguous remap, then 8-M-tile grouping; split tiles
+// take two consecutive blocks.
+__device__ __forceinline__ GmTile gm_tile_coords(int bid, int tiles_m, int tiles_n, int nwg, int full,
+                                                 int group_m) {
+  GmTile t;
+  t.khalf = -1;
   if (bid < full) {
-    const int xcd = bid & 7, loc = bid >> 3, q8 = full >> 3, r8 = full & 7;
-    pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    t.pid = gm_xcd_run_start<1>(bid, full) + (bid >> 3);
   } else {
     // split tiles: the same XCD-contiguous remap over the tail's blocks, so
     // an XCD runs both K-halves of a contiguous run of tiles (their A / B
     // panels share its L2) instead of one half of every 4th tile
-    const int t = bid - full, nt2 = nwg - full;
-    const int n2 = 2 * nt2;                        // blocks of the tail
-    const int xcd = t & 7, loc = t >> 3, q8 = n2 >> 3, r8 = n2 & 7;
-    const int j = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    pid = full + (j >> 1);
-    khalf = j & 1;
+    const int b = bid - full;
+    const int j = gm_xcd_run_start<2>(b, nwg - full) + (b >> 3);
+    t.pid = full + (j >> 1);
+    t.khalf = j & 1;
   }
-  const int group = pid / (group_m * tiles_n);
+  const int group = t.pid / (group_m * tiles_n);
   const int first_m = group * group_m;
   const int gsize = min(tiles_m - first_m, group_m);
-  const int tm = first_m + (pid % (group_m * tiles_n)) % gsize;
-  const int tn = (pid % (group_m * tiles_n)) / gsize;
+  t.tm = first_m + (t.pid % (group_m * tiles_n)) % gsize;
+  t.tn = (t.pid % (group_m * tiles_n)) / gsize;
+  return t;
+}
+
+// ------------------------------------------------------------ split-K hand-over
+// Split tile ``tix``: the first K-half to finish hands its accumulators over
+// and returns true (the block is done); the second adds them to its own and
+// returns false (it runs the epilogue).
+__device__ __forceinline__ bool gm_split_join(uint8_t* __restrict__ smem, gm_acc_t& acc, const GmSplit& sp,
+                                              int tix) {
+  const int tid = threadIdx.x;
+  int* cnt = sp.cnt + 2 * tix;
+  if (tid == 0) *reinterpret_cast<int*>(smem) =
+      __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  const int ticket = *reinterpret_cast<volatile int*>(smem);
+  __syncthreads();
+  // The slab moves with agent-scope (sc1) stores / loads -- written through
+  // and read past this XCD's L2 (the halves run on different XCDs) -- so
+  // neither side needs the whole-L2 write-back / invalidate of an
+  // agent-scope fence (measured: 156 vs 160 us at T=4041, fences cost L2
+  // hits for every block on the XCD).  Order: all slab stores acknowledged
+  // (vmcnt 0) -> barrier -> ready flag; the reader sees the flag before
+  // its barrier and then loads.
+  float* slab = sp.ws + (size_t)tix * GM_THREADS * 128;
+  const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, GM_THREADS * 32 * 16, 0x00020000);
+  if (ticket == 0) {                             // first: publish, then leave
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int d = 0; d < 2; ++d)
+          {
+            const int i = ((a * 4 + b) * 4 + c * 2 + d) * GM_THREADS + tid;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gm_u32x4, acc[a][b][c][d]), srs, i * 16,
+                                                   0, GM_CPOL_SC1);
+          }
+    GM_VMCNT(0);
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(cnt + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+  }
+  if (tid == 0) {                                // second: wait for the slab (bounded)
+    for (int spin = 0; spin < (1 << 24); ++spin) {
+      if (__hip_atomic_load(cnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+      __builtin_amdgcn_s_sleep(2);
+    }
+    GM_VMCNT(0);
+    // both halves are done with the counters: leave them zeroed for the next launch
+    __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(cnt + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+        {
+          const int i = ((a * 4 + b) * 4 + c * 2 + d) * GM_THREADS + tid;
+          acc[a][b][c][d] += __builtin_bit_cast(gm_f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                 srs, i * 16, 0, GM_CPOL_SC1));
+        }
+  return false;
+}
+
+
+// ------------------------------------------------------------ the tile
+// One output tile (or one K-half of a split tile): block ``bid`` of the
+// launch's block order.  In order: tile coordinates (gm_tile_coords), the
+// main loop (operand addresses, prologue, steady 8-phase loop, drain), the
+// split-K join (gm_split_join), then one `if constexpr` branch per epilogue
+// family.  The main loop and the epilogues stay in this one function on
+// purpose: hoisting either into a function of its own changes the kernels'
+// register allocation (profiles/gemm_refactor.md).
+template <int EPI, int DIAG>
+__device__ __forceinline__ void gemm_tile(
+    uint8_t* __restrict__ smem, const uint16_t* __restrict__ A, const uint16_t* __restrict__ W,
+    uint16_t* __restrict__ C, int M, int N, int K, int group_m, const float* __restrict__ rs, const GmRope& rp,
+    const GmSplit& sp, const GmSide& am, const int bid) {
+  constexpr bool kStamp = DIAG == GM_DIAG_CLOCK || DIAG == GM_DIAG_CLOCK_NO_DMA;
+  const int tiles_m = (M + GM_BM - 1) / GM_BM;
+  const int tiles_n = N / GM_BN;
+  const int nwg = tiles_m * tiles_n;
+  const int full = sp.ws ? sp.full : nwg;          // tiles [full, nwg) run split-K
+  const GmTile tile = gm_tile_coords(bid, tiles_m, tiles_n, nwg, full, group_m);
+  const int pid = tile.pid, khalf = tile.khalf, tm = tile.tm, tn = tile.tn;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // SCHED 8 / 9 (diagnostics): shader-clock and 100 MHz reference stamps at
+  // GM_DIAG_CLOCK*: shader-clock and 100 MHz reference stamps at
   // entry and exit, written by thread 0 to am.pv as 4 x u64 per block --
   // the in-kernel clock = d(memtime) / d(memrealtime) x 100 MHz, unprofiled
   // (MI355X_MICROARCH.md 'DVFS give-back' item 6)
   uint64_t st_t0 = 0, st_r0 = 0;
-  if constexpr (SCHED == 8 || SCHED == 9) {
+  if constexpr (kStamp) {
     st_t0 = __builtin_amdgcn_s_memtime();
     st_r0 = __builtin_amdgcn_s_memrealtime();
   }
@@ -239,9 +368,8 @@ __device__ __forceinline__ void gemm_tile(
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, M * K * 2, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, N * K * 2, 0x00020000);
   uint32_t va[2][2], vb[2][2];                     // byte offsets (row, chunk) of K-tile 0
-  // SCHED 10 (diagnostic, wrong numerics): every block stages the panels of
-  // tile (0, 0), so nearly every staging read hits the XCD's L2
-  const int ltm = SCHED == 10 ? 0 : tm, ltn = SCHED == 10 ? 0 : tn;
+  // (GM_DIAG_L2_PANELS: the panels of tile (0, 0), so nearly every staging read hits the XCD's L2)
+  const int ltm = DIAG == GM_DIAG_L2_PANELS ? 0 : tm, ltn = DIAG == GM_DIAG_L2_PANELS ? 0 : tn;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -269,7 +397,7 @@ __device__ __forceinline__ void gemm_tile(
     boff[1][kk] = boff[0][kk] + GM_BUF_BYTES;
   }
 
-  gm_f32x4 acc[2][4][2][2];                        // [mh][m][nh][n]
+  gm_acc_t acc;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -281,8 +409,12 @@ __device__ __forceinline__ void gemm_tile(
 
   gm_bf16x8 af[4][2];                              // one m-half: [m][kk]
   gm_bf16x8 bfr[2][2][2];                          // both n-halves: [nh][n][kk]
-  gm_bf16x8 b0y[2][2];                             // SCHED >= 1: buffer-1 B0 fragments
+  gm_bf16x8 b0y[2][2];                             // buffer 1's B0 fragments ([nh = 0] of bfr: buffer 0's)
+  // K-tiles of this block: all, or one half for a split tile (host: nt % 4 == 0)
+  const int nt = khalf < 0 ? K / GM_BK : K / GM_BK / 2;
+  const int kt0 = khalf > 0 ? nt : 0;
 
+  // ---- the phase macros (every name they use is declared above)
 #define GM_STAGE(BUF, HALF, KT)                                                               \
   do {                                                                                        \
     const uint32_t _ko = (uint32_t)((KT) + kt0) * (GM_BK * 2);                                \
@@ -307,18 +439,7 @@ __device__ __forceinline__ void gemm_tile(
         bfr[NH][n][kk] = *reinterpret_cast<const gm_bf16x8*>(smem + boff[BUF][kk] + (NH) * GM_HALF_BYTES + n * 2048); \
   } while (0)
 
-#define GM_MFMA(MH, NH)                                                                        \
-  do {                                                                                         \
-    __builtin_amdgcn_s_setprio(1);                                                             \
-    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                           \
-      _Pragma("unroll") for (int m = 0; m < 4; ++m)                                            \
-        _Pragma("unroll") for (int n = 0; n < 2; ++n)                                          \
-          acc[MH][m][NH][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m][kk], bfr[NH][n][kk], \
-                                                                      acc[MH][m][NH][n], 0, 0, 0); \
-    __builtin_amdgcn_s_setprio(0);                                                             \
-  } while (0)
-
-// SCHED >= 1 helpers: B0 fragments into an explicit register set, MFMA with it
+// B0 fragments into an explicit register set, MFMA with it
 #define GM_READ_B0_INTO(BUF, DST)                                                              \
   do {                                                                                         \
     _Pragma("unroll") for (int n = 0; n < 2; ++n)                                              \
@@ -328,67 +449,12 @@ __device__ __forceinline__ void gemm_tile(
 
 #define GM_MFMA_WITH(MH, NH, BREG)                                                             \
   do {                                                                                         \
-    if constexpr (SCHED == 1) __builtin_amdgcn_s_setprio(1);                                   \
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                           \
       _Pragma("unroll") for (int m = 0; m < 4; ++m)                                            \
         _Pragma("unroll") for (int n = 0; n < 2; ++n)                                          \
           acc[MH][m][NH][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m][kk], BREG[n][kk],  \
                                                                       acc[MH][m][NH][n], 0, 0, 0); \
-    if constexpr (SCHED == 1) __builtin_amdgcn_s_setprio(0);                                   \
   } while (0)
-
-#define GM_LGKM(N) asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory")
-#define GM_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-
-  // K-tiles of this block: all, or one half for a split tile (host: nt % 4 == 0)
-  const int nt = khalf < 0 ? K / GM_BK : K / GM_BK / 2;
-  const int kt0 = khalf > 0 ? nt : 0;
-
-  if constexpr (SCHED >= 1) {
-    // Wave priority.  SCHED 2 (default): one static s_setprio 1 for wave row
-    // 1 (the later-dispatched half, cdna_hip_programming.md T5 static form),
-    // no per-cluster flips -- 1.7 % faster than SCHED 1 (s_setprio 1 around
-    // every MFMA cluster) at T = 4041 (profiles/r2_gemm_prio_ab.jsonl).
-    // SCHED 3 / 4 (A/B only): the static priority on wave row 0 / none.
-    if constexpr (SCHED == 2 || SCHED == 3 || SCHED >= 5) {
-      if (wr == (SCHED == 3 ? 0 : 1)) __builtin_amdgcn_s_setprio(1);
-    }
-    // Balanced schedule: every phase retires the half-tile staged 3 phases
-    // earlier (vmcnt(6) each phase), so the NEXT buffer's B0 fragments can be
-    // read one phase early (phases 4 and 8, which otherwise read nothing):
-    // 8/4/8/4 fragment reads per phase instead of 12/4/8/0.  Stage order per
-    // buffer is B0, A0, B1, A1; every restage is >= 2 phases after the
-    // half-tile's last read (safe with the wave-row stagger).
-    if constexpr (EPI == GM_EPI_RESID_PRE) {
-      // the residual rows 0-31 of this wave's output block -> spare LDS; the
-      // prologue's counted vmcnt waits retire them with the first half-tiles
-      const int col0p = tn * GM_BN + wc * 64, row0p = tm * GM_BM + wr * 128;
-      const __amdgpu_buffer_rsrc_t rsp =
-          __builtin_amdgcn_make_buffer_rsrc((void*)C, 0, (uint32_t)M * (uint32_t)N * 2u, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = i * 8 + (lane >> 3), c = lane & 7;
-        const uint32_t vo = ((uint32_t)(row0p + r) * (uint32_t)N + (uint32_t)(col0p + c * 8)) * 2u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsp, (gm_lds_ptr)(smem + GM_LDS_BYTES + w * 4096 + i * 1024), 16,
-                                                 vo, 0, 0, 0);
-      }
-    }
-    GM_STAGE(0, GM_B0, 0);
-    GM_STAGE(0, GM_A0, 0);
-    GM_STAGE(0, GM_B1, 0);
-    GM_STAGE(0, GM_A1, 0);
-    GM_STAGE(1, GM_B0, 1);
-    GM_STAGE(1, GM_A0, 1);
-    GM_STAGE(1, GM_B1, 1);
-    GM_VMCNT(6);
-    GM_BARRIER();
-    GM_READ_B0_INTO(0, bfr[0]);
-    if constexpr (SCHED >= 5 && SCHED <= 7) {      // diagnostics: every fragment register defined
-      GM_READ_A(0, 0);
-      GM_READ_B(0, 1);
-      GM_READ_B0_INTO(1, b0y);
-    }
-    if (STAGGER && wr == 1) GM_BARRIER();
 
 #define GM_PHASE_END(MH, NH, BREG) \
   do {                             \
@@ -398,203 +464,106 @@ __device__ __forceinline__ void gemm_tile(
     GM_BARRIER();                  \
   } while (0)
 
-    int t = 0;
-    // SCHED 5-7: power/energy DIAGNOSTICS only (bench/gemm_energy_diag.hip; wrong
-    // numerics, never dispatched by the library): 5 skips the A fragment
-    // reads of phases 3 / 7 (one third fewer LDS read bytes, what a 128x128
-    // wave tile would read), 6 skips every fragment read of the loop, 7 skips
-    // every staging DMA of the loop (no L2 / HBM traffic in steady state).
-    // SCHED 8 / 9: production / no-DMA with in-kernel clock stamps (below).
-    constexpr bool kRdA = SCHED != 6, kRdA2 = SCHED != 5 && SCHED != 6, kRdB = SCHED != 6;
-    constexpr bool kDma = SCHED != 7 && SCHED != 9;
-#define GM_D_READ_A(C, B, H) do { if constexpr (C) GM_READ_A(B, H); } while (0)
+  // ---- main loop: prologue
+  // Wave priority: one static s_setprio 1 for wave row 1 (the
+  // later-dispatched half, cdna_hip_programming.md T5 static form), no
+  // per-cluster flips -- 1.7 % faster than s_setprio 1 around every MFMA
+  // cluster at T = 4041; the static priority on wave row 0, or none, lost too
+  // (profiles/r2_gemm_prio_ab.jsonl).
+  if (wr == 1) __builtin_amdgcn_s_setprio(1);
+  // Balanced schedule: every phase retires the half-tile staged 3 phases
+  // earlier (vmcnt(6) each phase), so the NEXT buffer's B0 fragments can be
+  // read one phase early (phases 4 and 8, which otherwise read nothing):
+  // 8/4/8/4 fragment reads per phase instead of 12/4/8/0.  Stage order per
+  // buffer is B0, A0, B1, A1; every restage is >= 2 phases after the
+  // half-tile's last read (safe with the wave-row stagger).
+  if constexpr (EPI == GM_EPI_RESID_PRE) {
+    // the residual rows 0-31 of this wave's output block -> spare LDS; the
+    // prologue's counted vmcnt waits retire them with the first half-tiles
+    const int col0p = tn * GM_BN + wc * 64, row0p = tm * GM_BM + wr * 128;
+    const __amdgpu_buffer_rsrc_t rsp =
+        __builtin_amdgcn_make_buffer_rsrc((void*)C, 0, (uint32_t)M * (uint32_t)N * 2u, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = i * 8 + (lane >> 3), c = lane & 7;
+      const uint32_t vo = ((uint32_t)(row0p + r) * (uint32_t)N + (uint32_t)(col0p + c * 8)) * 2u;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsp, (gm_lds_ptr)(smem + GM_LDS_BYTES + w * 4096 + i * 1024), 16,
+                                               vo, 0, 0, 0);
+    }
+  }
+  GM_STAGE(0, GM_B0, 0);
+  GM_STAGE(0, GM_A0, 0);
+  GM_STAGE(0, GM_B1, 0);
+  GM_STAGE(0, GM_A1, 0);
+  GM_STAGE(1, GM_B0, 1);
+  GM_STAGE(1, GM_A0, 1);
+  GM_STAGE(1, GM_B1, 1);
+  GM_VMCNT(6);
+  GM_BARRIER();
+  GM_READ_B0_INTO(0, bfr[0]);
+  if constexpr (DIAG >= GM_DIAG_SKIP_A2 && DIAG <= GM_DIAG_NO_DMA) {   // every fragment register defined
+    GM_READ_A(0, 0);
+    GM_READ_B(0, 1);
+    GM_READ_B0_INTO(1, b0y);
+  }
+  // wave-row 1 runs half a phase behind wave-row 0: on every SIMD (one wave
+  // of each row) one wave's fragment reads + DMA issue overlap the other's
+  // MFMA cluster.  One extra barrier here, balanced after the loop.
+  if (wr == 1) GM_BARRIER();
+
+  // ---- main loop: steady state, two K-tiles = eight phases per trip.  The
+  // GM_D_* forms are the diagnostics' switches (GM_DIAG_*): which fragment
+  // reads and staging DMAs the steady loop issues
+  int t = 0;
+  constexpr bool kRdA = DIAG != GM_DIAG_NO_LDS_READ;
+  constexpr bool kRdA2 = DIAG != GM_DIAG_SKIP_A2 && DIAG != GM_DIAG_NO_LDS_READ;
+  constexpr bool kRdB = DIAG != GM_DIAG_NO_LDS_READ;
+  constexpr bool kDma = DIAG != GM_DIAG_NO_DMA && DIAG != GM_DIAG_CLOCK_NO_DMA;
+#define GM_D_READ_A(ON, B, H) do { if constexpr (ON) GM_READ_A(B, H); } while (0)
 #define GM_D_READ_B(B, H) do { if constexpr (kRdB) GM_READ_B(B, H); } while (0)
 #define GM_D_READ_B0(B, D) do { if constexpr (kRdB) GM_READ_B0_INTO(B, D); } while (0)
 #define GM_D_STAGE(B, H, K) do { if constexpr (kDma) GM_STAGE(B, H, K); } while (0)
-    for (; t < nt - 2; t += 2) {
-      {
-        GM_D_READ_A(kRdA, 0, 0); GM_D_STAGE(1, GM_A1, t + 1); GM_VMCNT(6); GM_PHASE_END(0, 0, bfr[0]);
-        GM_D_READ_B(0, 1); GM_D_STAGE(0, GM_B0, t + 2); GM_VMCNT(6); GM_PHASE_END(0, 1, bfr[1]);
-        GM_D_READ_A(kRdA2, 0, 1); GM_D_STAGE(0, GM_A0, t + 2); GM_VMCNT(6); GM_PHASE_END(1, 1, bfr[1]);
-        GM_D_READ_B0(1, b0y); GM_D_STAGE(0, GM_B1, t + 2); GM_VMCNT(6); GM_PHASE_END(1, 0, bfr[0]);
-        GM_D_READ_A(kRdA, 1, 0); GM_D_STAGE(0, GM_A1, t + 2); GM_VMCNT(6); GM_PHASE_END(0, 0, b0y);
-        GM_D_READ_B(1, 1); GM_D_STAGE(1, GM_B0, t + 3); GM_VMCNT(6); GM_PHASE_END(0, 1, bfr[1]);
-        GM_D_READ_A(kRdA2, 1, 1); GM_D_STAGE(1, GM_A0, t + 3); GM_VMCNT(6); GM_PHASE_END(1, 1, bfr[1]);
-        GM_D_READ_B0(0, bfr[0]); GM_D_STAGE(1, GM_B1, t + 3); GM_VMCNT(6); GM_PHASE_END(1, 0, b0y);
-      }
+  for (; t < nt - 2; t += 2) {
+    {
+      GM_D_READ_A(kRdA, 0, 0); GM_D_STAGE(1, GM_A1, t + 1); GM_VMCNT(6); GM_PHASE_END(0, 0, bfr[0]);
+      GM_D_READ_B(0, 1); GM_D_STAGE(0, GM_B0, t + 2); GM_VMCNT(6); GM_PHASE_END(0, 1, bfr[1]);
+      GM_D_READ_A(kRdA2, 0, 1); GM_D_STAGE(0, GM_A0, t + 2); GM_VMCNT(6); GM_PHASE_END(1, 1, bfr[1]);
+      GM_D_READ_B0(1, b0y); GM_D_STAGE(0, GM_B1, t + 2); GM_VMCNT(6); GM_PHASE_END(1, 0, bfr[0]);
+      GM_D_READ_A(kRdA, 1, 0); GM_D_STAGE(0, GM_A1, t + 2); GM_VMCNT(6); GM_PHASE_END(0, 0, b0y);
+      GM_D_READ_B(1, 1); GM_D_STAGE(1, GM_B0, t + 3); GM_VMCNT(6); GM_PHASE_END(0, 1, bfr[1]);
+      GM_D_READ_A(kRdA2, 1, 1); GM_D_STAGE(1, GM_A0, t + 3); GM_VMCNT(6); GM_PHASE_END(1, 1, bfr[1]);
+      GM_D_READ_B0(0, bfr[0]); GM_D_STAGE(1, GM_B1, t + 3); GM_VMCNT(6); GM_PHASE_END(1, 0, b0y);
     }
+  }
+  {                                              // ---- main loop: drain, the last two K-tiles
+      GM_READ_A(0, 0); GM_STAGE(1, GM_A1, t + 1); GM_VMCNT(6); GM_PHASE_END(0, 0, bfr[0]);
+      GM_READ_B(0, 1); GM_VMCNT(4); GM_PHASE_END(0, 1, bfr[1]);
+      GM_READ_A(0, 1); GM_VMCNT(2); GM_PHASE_END(1, 1, bfr[1]);
+      GM_READ_B0_INTO(1, b0y); GM_VMCNT(0); GM_PHASE_END(1, 0, bfr[0]);
+      GM_READ_A(1, 0); GM_PHASE_END(0, 0, b0y);
+      GM_READ_B(1, 1); GM_PHASE_END(0, 1, bfr[1]);
+      GM_READ_A(1, 1); GM_PHASE_END(1, 1, bfr[1]);
+      GM_PHASE_END(1, 0, b0y);
+  }
+  __builtin_amdgcn_s_setprio(0);
+  if (wr == 0) GM_BARRIER();                       // balances the stagger's extra barrier
 #undef GM_D_READ_A
 #undef GM_D_READ_B
 #undef GM_D_READ_B0
 #undef GM_D_STAGE
-    {                                              // last two K-tiles: drain
-        GM_READ_A(0, 0); GM_STAGE(1, GM_A1, t + 1); GM_VMCNT(6); GM_PHASE_END(0, 0, bfr[0]);
-        GM_READ_B(0, 1); GM_VMCNT(4); GM_PHASE_END(0, 1, bfr[1]);
-        GM_READ_A(0, 1); GM_VMCNT(2); GM_PHASE_END(1, 1, bfr[1]);
-        GM_READ_B0_INTO(1, b0y); GM_VMCNT(0); GM_PHASE_END(1, 0, bfr[0]);
-        GM_READ_A(1, 0); GM_PHASE_END(0, 0, b0y);
-        GM_READ_B(1, 1); GM_PHASE_END(0, 1, bfr[1]);
-        GM_READ_A(1, 1); GM_PHASE_END(1, 1, bfr[1]);
-        GM_PHASE_END(1, 0, b0y);
-    }
-    if constexpr (SCHED == 2 || SCHED == 3 || SCHED >= 5) __builtin_amdgcn_s_setprio(0);
 #undef GM_PHASE_END
-  } else {
-    // prologue: tile 0 -> buffer 0 (all halves), tile 1 -> buffer 1 (B0, A0, B1)
-    GM_STAGE(0, GM_A0, 0);
-    GM_STAGE(0, GM_A1, 0);
-    GM_STAGE(0, GM_B0, 0);
-    GM_STAGE(0, GM_B1, 0);
-    GM_STAGE(1, GM_B0, 1);
-    GM_STAGE(1, GM_A0, 1);
-    GM_STAGE(1, GM_B1, 1);
-    GM_VMCNT(6);
-    GM_BARRIER();
-    // wave-row 1 runs half a phase behind wave-row 0: on every SIMD (one wave
-    // of each row) one wave's fragment reads + DMA issue overlap the other's
-    // MFMA cluster.  One extra barrier here, balanced after the loop.
-    if (STAGGER && wr == 1) GM_BARRIER();
-
-    for (int t = 0; t < nt; t += 2) {
-      const bool more = t + 2 < nt;                  // wave-uniform
-      // ---- phase 1: buffer 0 quadrant (0,0); stage buffer 1 A1 (tile t+1)
-      GM_READ_B(0, 0);
-      GM_FENCE();
-      GM_READ_A(0, 0);
-      GM_STAGE(1, GM_A1, t + 1);
-      GM_LGKM(8);
-      GM_BARRIER();
-      GM_LGKM(0);
-      GM_MFMA(0, 0);
-      GM_BARRIER();
-      // ---- phase 2: quadrant (0,1); stage buffer 0 B0 (tile t+2)
-      GM_READ_B(0, 1);
-      if (more) GM_STAGE(0, GM_B0, t + 2);
-      GM_BARRIER();
-      GM_LGKM(0);
-      GM_MFMA(0, 1);
-      GM_BARRIER();
-      // ---- phase 3: quadrant (1,1); stage buffer 0 A0
-      GM_READ_A(0, 1);
-      if (more) GM_STAGE(0, GM_A0, t + 2);
-      GM_BARRIER();
-      GM_LGKM(0);
-      GM_MFMA(1, 1);
-      GM_BARRIER();
-      // ---- phase 4: quadrant (1,0); stage buffer 0 B1; retire buffer 1
-      if (more) {
-        GM_STAGE(0, GM_B1, t + 2);
-        GM_VMCNT(6);
-      } else {
-        GM_VMCNT(0);
-      }
-      GM_BARRIER();
-      GM_MFMA(1, 0);
-      GM_BARRIER();
-      // ---- phase 5: buffer 1 quadrant (0,0); stage buffer 0 A1
-      GM_READ_B(1, 0);
-      GM_FENCE();
-      GM_READ_A(1, 0);
-      if (more) GM_STAGE(0, GM_A1, t + 2);
-      GM_LGKM(8);
-      GM_BARRIER();
-      GM_LGKM(0);
-      GM_MFMA(0, 0);
-      GM_BARRIER();
-      // ---- phase 6: quadrant (0,1); stage buffer 1 B0 (tile t+3)
-      GM_READ_B(1, 1);
-      if (more) GM_STAGE(1, GM_B0, t + 3);
-      GM_BARRIER();
-      GM_LGKM(0);
-      GM_MFMA(0, 1);
-      GM_BARRIER();
-      // ---- phase 7: quadrant (1,1); stage buffer 1 A0
-      GM_READ_A(1, 1);
-      if (more) GM_STAGE(1, GM_A0, t + 3);
-      GM_BARRIER();
-      GM_LGKM(0);
-      GM_MFMA(1, 1);
-      GM_BARRIER();
-      // ---- phase 8: quadrant (1,0); stage buffer 1 B1; retire buffer 0
-      if (more) {
-        GM_STAGE(1, GM_B1, t + 3);
-        GM_VMCNT(6);
-      }
-      GM_BARRIER();
-      GM_MFMA(1, 0);
-      GM_BARRIER();
-    }
-  }
-
-
-  if (STAGGER && wr == 0) GM_BARRIER();
+#undef GM_MFMA_WITH
+#undef GM_READ_B0_INTO
+#undef GM_READ_B
+#undef GM_READ_A
+#undef GM_STAGE
 
   // ---- split tile: the first K-half to finish hands its accumulators over
-  if (khalf >= 0) {
-    const int tix = pid - full;
-    int* cnt = sp.cnt + 2 * tix;
-    if (tid == 0) *reinterpret_cast<int*>(smem) =
-        __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const int ticket = *reinterpret_cast<volatile int*>(smem);
-    __syncthreads();
-    // The slab moves with agent-scope (sc1) stores / loads -- written through
-    // and read past this XCD's L2 (the halves run on different XCDs) -- so
-    // neither side needs the whole-L2 write-back / invalidate of an
-    // agent-scope fence (measured: 156 vs 160 us at T=4041, fences cost L2
-    // hits for every block on the XCD).  Order: all slab stores acknowledged
-    // (vmcnt 0) -> barrier -> ready flag; the reader sees the flag before
-    // its barrier and then loads.
-    float* slab = sp.ws + (size_t)tix * GM_THREADS * 128;
-    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, GM_THREADS * 32 * 16, 0x00020000);
-    if (ticket == 0) {                             // first: publish, then leave
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int d = 0; d < 2; ++d)
-            {
-              const int i = ((a * 4 + b) * 4 + c * 2 + d) * GM_THREADS + tid;
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gm_u32x4, acc[a][b][c][d]), srs, i * 16,
-                                                     0, GM_CPOL_SC1);
-            }
-      GM_VMCNT(0);
-      __syncthreads();
-      if (tid == 0) __hip_atomic_store(cnt + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-    if (tid == 0) {                                // second: wait for the slab (bounded)
-      for (int spin = 0; spin < (1 << 24); ++spin) {
-        if (__hip_atomic_load(cnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        __builtin_amdgcn_s_sleep(2);
-      }
-      GM_VMCNT(0);
-      // both halves are done with the counters: leave them zeroed for the next launch
-      __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(cnt + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int d = 0; d < 2; ++d)
-          {
-            const int i = ((a * 4 + b) * 4 + c * 2 + d) * GM_THREADS + tid;
-            acc[a][b][c][d] += __builtin_bit_cast(gm_f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                   srs, i * 16, 0, GM_CPOL_SC1));
-          }
-  }
+  if (khalf >= 0 && gm_split_join(smem, acc, sp, pid - full)) return;
 
   // ---- epilogue through LDS (the staging buffers are free after the last barrier)
   const int row0 = tm * GM_BM + wr * 128;          // first output row of this wave
-  if (EPI == GM_EPI_ARGMAX || EPI == GM_EPI_SAMPLE) {
+  if constexpr (EPI == GM_EPI_ARGMAX || EPI == GM_EPI_SAMPLE) {
     if constexpr (EPI == GM_EPI_SAMPLE) {
       // score = acc / T + Gumbel(key[row], column) in place; the row inputs
       // of this lane's 32 rows come as whole-tile vector loads (padded
@@ -666,7 +635,7 @@ __device__ __forceinline__ void gemm_tile(
         am.pi[(int64_t)grow * tiles_n + tn] = tn * GM_BN + c;
       }
     }
-  } else if (EPI == GM_EPI_RESID) {
+  } else if constexpr (EPI == GM_EPI_RESID) {
     // fp32 through LDS in four passes of 32 rows (8.5 KiB per wave, row
     // stride 68 floats: the four fq row groups of a write land on distinct
     // banks), then coalesced: 16 B of fp32 + 8 B of the bf16 residual per
@@ -721,7 +690,7 @@ __device__ __forceinline__ void gemm_tile(
         GM_LGKM(0);
         __builtin_amdgcn_wave_barrier();
       }
-  } else if (EPI == GM_EPI_RESID_LDS || EPI == GM_EPI_RESID_PRE || EPI == GM_EPI_RESID_RMS) {
+  } else if constexpr (EPI == GM_EPI_RESID_LDS || EPI == GM_EPI_RESID_PRE || EPI == GM_EPI_RESID_RMS) {
     // The residual tile staged by DMA instead of through registers: the
     // wave's 128 x 64 bf16 block of C lands in its 16 KiB of LDS (16
     // buffer_load ... lds of 16 B per lane, row-major, the plain epilogue's
@@ -833,7 +802,7 @@ __device__ __forceinline__ void gemm_tile(
         if (tid == 0) __hip_atomic_store(am.rticket + tm, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-  } else if (EPI == GM_EPI_SWIGLU) {
+  } else if constexpr (EPI == GM_EPI_SWIGLU) {
     // wave w: 128 rows x 32 features bf16 = 8 KiB at w * 8 KiB
     uint16_t* o = reinterpret_cast<uint16_t*>(smem + w * 8192);
     gm_f32x4 sc[2][4];
@@ -880,7 +849,7 @@ __device__ __forceinline__ void gemm_tile(
             for (int j = 0; j < 4; ++j)
               o[(mh * 64 + m * 16 + fq * 4 + j) * 64 + nh * 32 + n * 16 + fr] =
                   gm_f2bf(acc[mh][m][nh][n][j] * sc[mh][m][j]);
-    if (EPI == GM_EPI_STORE) {
+    if constexpr (EPI == GM_EPI_STORE) {
       GM_LGKM(0);
       __builtin_amdgcn_wave_barrier();
       const int col0 = tn * GM_BN + wc * 64;
@@ -971,7 +940,7 @@ __device__ __forceinline__ void gemm_tile(
       }
     }
   }
-  if constexpr (SCHED == 8 || SCHED == 9) {
+  if constexpr (kStamp) {
     const uint64_t st_t1 = __builtin_amdgcn_s_memtime(), st_r1 = __builtin_amdgcn_s_memrealtime();
     if (tid == 0 && am.pv != nullptr) {
       uint64_t* dbg = reinterpret_cast<uint64_t*>(am.pv) + (size_t)bid * 4;
@@ -983,31 +952,15 @@ __device__ __forceinline__ void gemm_tile(
   }
 }
 
-// PERSIST: the grid (host: at most one block per CU the stream can use, so
-// every block is resident -- a split tile's second half may wait for its
-// first) walks the block order with stride gridDim.x.  Block b keeps XCD
-// b % 8 (gridDim.x % 8 == 0), so the XCD-contiguous tile runs are unchanged;
-// what changes is that a tile's epilogue stores drain while the same block
-// issues the next tile's prologue DMA, instead of the CU idling between a
-// block's exit and the next block's first loads.
-template <int EPI, bool STAGGER = true, int SCHED = 2, bool PERSIST = false>
+// DIAG != GM_DIAG_NONE only from bench/gemm_energy_diag.hip
+template <int EPI, int DIAG = GM_DIAG_NONE>
 __global__ __launch_bounds__(GM_THREADS) void gemm_bf16_kernel(
     const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, uint16_t* __restrict__ C,
     int M, int N, int K, int group_m, const float* __restrict__ rs, const GmRope rp, const GmSplit sp,
     const GmSide am) {
   extern __shared__ __align__(16) uint8_t smem[];
-  if constexpr (PERSIST) {
-    const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
-    const int nb = sp.ws ? sp.full + 2 * (tiles - sp.full) : tiles;
-    for (int vb = blockIdx.x; vb < nb; vb += gridDim.x) {
-      gemm_tile<EPI, STAGGER, SCHED>(smem, A, W, C, M, N, K, group_m, rs, rp, sp, am, vb);
-      __syncthreads();                             // the tile's LDS reads retire before the next DMA
-    }
-  } else {
-    gemm_tile<EPI, STAGGER, SCHED>(smem, A, W, C, M, N, K, group_m, rs, rp, sp, am, (int)blockIdx.x);
-  }
+  gemm_tile<EPI, DIAG>(smem, A, W, C, M, N, K, group_m, rs, rp, sp, am, (int)blockIdx.x);
 }
-
 
 // out[row] = column of the first maximum over the tiles' partials (one wave per row)
 __global__ __launch_bounds__(256) void gemm_argmax_reduce_kernel(const float* __restrict__ pv,
@@ -1040,12 +993,6 @@ __global__ __launch_bounds__(256) void sample_bits_kernel(const uint32_t* __rest
   if (i < count) out[(int64_t)k * count + i] = sn_bits(keys[2 * k], keys[2 * k + 1], n0 + (uint32_t)i);
 }
 
-#undef GM_STAGE
-#undef GM_READ_A
-#undef GM_READ_B
-#undef GM_MFMA
-#undef GM_READ_B0_INTO
-#undef GM_MFMA_WITH
 #undef GM_LGKM
 #undef GM_VMCNT
 #undef GM_BARRIER

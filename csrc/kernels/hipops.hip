@@ -42,6 +42,10 @@ static void check_launch() { HIP_CHECK(hipGetLastError()); }
 static void require(bool cond, const char* what) {
   if (!cond) throw std::invalid_argument(what);
 }
+// ... with the entry point's name in front of the message
+static void require_in(const char* fn, bool cond, const char* what) {
+  if (!cond) throw std::invalid_argument(std::string(fn) + ": " + what);
+}
 
 // ---------------------------------------------------------------------- text
 static void text_analyze(uintptr_t bytes, uintptr_t offsets, int B, int L, py::bytes table,
@@ -199,37 +203,48 @@ static void rmsnorm(uintptr_t x, uintptr_t res, uintptr_t w, uintptr_t y, int T,
   check_launch();
 }
 
-// C = A · Wᵀ (epi 0, C [M][N]) or H = silu(A·Wgᵀ) * (A·Wuᵀ) over a
-// swiglu-permuted W (epi 2, C [M][N/2]); A [M][K], W [N][K], bf16.
-// persist_cus > 0: the persistent form (gemm_bf16_kernel PERSIST) on a grid of
-// min(blocks, persist_cus) -- persist_cus must not exceed the CUs the stream
-// can run on (every block resident; a multiple of 8 keeps blocks on their XCD)
-template <int EPI, bool STAGGER = true, int SCHED = 2>
-static void launch_gemm(const uint16_t* a, const uint16_t* w, uint16_t* c, int M, int N, int K, hipStream_t st,
-                        int group_m, const float* rs = nullptr, const GmRope& rp = GmRope{},
-                        const GmSplit& sp = GmSplit{0, nullptr, nullptr},
-                        const GmSide& am = GmSide{}, int persist_cus = 0) {
-  static bool attr = false, attr_p = false;
+// ---------------------------------------------------------------------- 256 x 256 GEMM (gemm_kernels.h)
+// One block per tile, two per split tile (GmSplit); A [M][K], W [N][K], bf16.
+template <int EPI>
+static void launch_gemm(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, uintptr_t stream, int group_m,
+                        const float* rs = nullptr, const GmRope& rp = GmRope{},
+                        const GmSplit& sp = GmSplit{0, nullptr, nullptr}, const GmSide& am = GmSide{}) {
+  static bool attr = false;
   const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
   const int nb = sp.ws ? sp.full + 2 * (tiles - sp.full) : tiles;
-  if (persist_cus > 0 && nb > persist_cus) {
-    if (!attr_p) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI, STAGGER, SCHED, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, gm_lds_bytes<EPI>()));
-      attr_p = true;
-    }
-    hipLaunchKernelGGL((gemm_bf16_kernel<EPI, STAGGER, SCHED, true>), dim3(persist_cus), dim3(GM_THREADS),
-                       gm_lds_bytes<EPI>(), st, a, w, c, M, N, K, group_m, rs, rp, sp, am);
-    return;
-  }
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI, STAGGER, SCHED>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, gm_lds_bytes<EPI>()));
+    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  gm_lds_bytes<EPI>()));
     attr = true;
   }
-  hipLaunchKernelGGL((gemm_bf16_kernel<EPI, STAGGER, SCHED>), dim3(nb), dim3(GM_THREADS), gm_lds_bytes<EPI>(), st,
-                     a, w, c,
-                     M, N, K, group_m, rs, rp, sp, am);
+  hipLaunchKernelGGL((gemm_bf16_kernel<EPI>), dim3(nb), dim3(GM_THREADS), gm_lds_bytes<EPI>(), S(stream),
+                     P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, group_m, rs, rp, sp, am);
+}
+
+// What every entry point of the kernel checks (``fn`` names it in the
+// message).  c = 0: the epilogue writes no C; c_desc: it builds a buffer
+// descriptor over C, so M * N is bounded like the operands.
+static void check_gemm_operands(const char* fn, uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K,
+                                int group_m, bool c_desc) {
+  require_in(fn, group_m >= 1 && group_m <= 64, "group_m out of range");
+  require_in(fn, M > 0 && N > 0 && K > 0, "empty operand");
+  require_in(fn, N % GM_BN == 0, "N must be a multiple of 256");
+  require_in(fn, K % (2 * GM_BK) == 0, "K must be a multiple of 128");
+  require_in(fn, (int64_t)M * K < (int64_t)1 << 30 && (int64_t)N * K < (int64_t)1 << 30 &&
+                 (!c_desc || (int64_t)M * N < (int64_t)1 << 30),
+             "operand too large (2 GiB buffer descriptors)");
+  require_in(fn, a % 16 == 0 && w % 16 == 0 && c % 16 == 0, "pointers must be 16-byte aligned");
+}
+
+// split_ws != 0: tiles [split_full, tiles) run split-K over two blocks each
+static GmSplit make_split(const char* fn, int M, int N, int K, int split_full, uintptr_t split_ws,
+                          uintptr_t split_cnt) {
+  if (!split_ws) return GmSplit{0, nullptr, nullptr};
+  const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
+  require_in(fn, split_full >= 0 && split_full < tiles, "bad split");
+  require_in(fn, (K / GM_BK) % 4 == 0 && K / GM_BK >= 8, "split-K needs K % 256 == 0 and K >= 512");
+  require_in(fn, split_cnt != 0 && split_ws % 16 == 0, "split workspace");
+  return GmSplit{split_full, P<float>(split_ws), P<int>(split_cnt)};
 }
 
 // C += A·Wᵀ (GM_EPI_RESID_RMS = the LDS epilogue) and the RMSNorm scale of the updated rows in
@@ -238,92 +253,42 @@ static void launch_gemm(const uint16_t* a, const uint16_t* w, uint16_t* c, int M
 // row_rms_kernel writes, rows < M meaningful).
 static void gemm_residual_rms(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, uintptr_t stream,
                               int group_m, uintptr_t part, uintptr_t ticket, uintptr_t scale, float eps) {
-  require(group_m >= 1 && group_m <= 64, "gemm: group_m out of range");
-  require(M > 0 && N > 0 && K > 0, "gemm: empty operand");
-  require(N % GM_BN == 0, "gemm: N must be a multiple of 256");
-  require(K % (2 * GM_BK) == 0, "gemm: K must be a multiple of 128");
-  require((int64_t)M * K < (int64_t)1 << 30 && (int64_t)N * K < (int64_t)1 << 30 && (int64_t)M * N < (int64_t)1 << 30,
-          "gemm: operand too large (2 GiB buffer descriptors)");
-  require(a % 16 == 0 && w % 16 == 0 && c % 16 == 0, "gemm: pointers must be 16-byte aligned");
+  check_gemm_operands("gemm_residual_rms", a, w, c, M, N, K, group_m, true);
   require(part != 0 && ticket != 0 && scale != 0, "gemm_residual_rms: null workspace");
   GmSide side{};
   side.rpart = P<float>(part);
   side.rticket = P<int>(ticket);
   side.rscale = P<float>(scale);
   side.reps = eps;
-  launch_gemm<GM_EPI_RESID_RMS>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream),
-                                group_m, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, side);
+  launch_gemm<GM_EPI_RESID_RMS>(a, w, c, M, N, K, stream, group_m, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr},
+                                side);
   check_launch();
 }
 
-// epi: 0 / 2 / 5 = store / SwiGLU / residual add (C += A·Wᵀ); 16 / 32 = store with the round-1 phase
-// schedule / without the wave-row stagger; 50 / 66 / 82 = SwiGLU with
-// s_setprio around every MFMA cluster / the static priority on wave row 0 /
-// no priority (A/B only; the default is a static priority on wave row 1).
+// epi (GM_EPI_*): 0 = store (C [M][N]), 2 = SwiGLU over a swiglu-permuted W
+// (C [M][N/2]), 5 / 6 / 7 = residual add C += A·Wᵀ in place through registers
+// (A/B) / staged into LDS by DMA (default) / with its first quarter
+// prefetched at kernel start (A/B).  rs: per-row scales (store and SwiGLU).
 // split_ws != 0: tiles [split_full, tiles) run split-K over two blocks each
 // (GmSplit; epilogues store / SwiGLU / residual-LDS): a step too small to
 // fill its CUs with whole tiles -- the realtime micro-forwards on their CU
 // partition, where o / down are 16 tiles for 32 CUs.
-static int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return 0;
-  if (!cus[dev]) HIP_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-  return cus[dev];
-}
-
-constexpr int GM_PERSIST_FLAG = 256;   // epi | flag: the persistent grid (one block per CU of the device)
-
 static void gemm_bf16(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, int epi, uintptr_t stream,
                       int group_m, uintptr_t rs, int split_full, uintptr_t split_ws, uintptr_t split_cnt) {
-  const int pc = (epi & GM_PERSIST_FLAG) ? device_cus() & ~7 : 0;
-  epi &= ~GM_PERSIST_FLAG;
-  require(group_m >= 1 && group_m <= 64, "gemm: group_m out of range");
-  require(M > 0 && N > 0 && K > 0, "gemm: empty operand");
-  require(N % GM_BN == 0, "gemm: N must be a multiple of 256");
-  require(K % (2 * GM_BK) == 0, "gemm: K must be a multiple of 128");
-  require((int64_t)M * K < (int64_t)1 << 30 && (int64_t)N * K < (int64_t)1 << 30, "gemm: operand too large (2 GiB buffer descriptors)");
-  require(a % 16 == 0 && w % 16 == 0 && c % 16 == 0, "gemm: pointers must be 16-byte aligned");
+  const bool resid = epi == GM_EPI_RESID || epi == GM_EPI_RESID_LDS || epi == GM_EPI_RESID_PRE;
+  check_gemm_operands("gemm", a, w, c, M, N, K, group_m, resid);
   const float* rsp = rs ? P<const float>(rs) : nullptr;
-  GmSplit sp{0, nullptr, nullptr};
-  if (split_ws) {
-    const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
-    require(split_full >= 0 && split_full < tiles, "gemm: bad split");
-    require((K / GM_BK) % 4 == 0 && K / GM_BK >= 8, "gemm: split-K needs K % 256 == 0 and K >= 512");
-    require(split_cnt != 0 && split_ws % 16 == 0, "gemm: split workspace");
-    require(epi == GM_EPI_STORE || epi == GM_EPI_SWIGLU || epi == GM_EPI_RESID_LDS, "gemm: split-K epilogue");
-    sp = GmSplit{split_full, P<float>(split_ws), P<int>(split_cnt)};
+  const GmSplit sp = make_split("gemm", M, N, K, split_full, split_ws, split_cnt);
+  require(!resid || !rsp, "gemm: the residual epilogues take no row scale");
+  require(!sp.ws || epi == GM_EPI_STORE || epi == GM_EPI_SWIGLU || epi == GM_EPI_RESID_LDS, "gemm: split-K epilogue");
+  switch (epi) {
+    case GM_EPI_STORE: launch_gemm<GM_EPI_STORE>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
+    case GM_EPI_SWIGLU: launch_gemm<GM_EPI_SWIGLU>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
+    case GM_EPI_RESID: launch_gemm<GM_EPI_RESID>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
+    case GM_EPI_RESID_LDS: launch_gemm<GM_EPI_RESID_LDS>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
+    case GM_EPI_RESID_PRE: launch_gemm<GM_EPI_RESID_PRE>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
+    default: throw std::invalid_argument("gemm: unknown epilogue");
   }
-  if (epi == GM_EPI_STORE)
-    launch_gemm<GM_EPI_STORE>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream), group_m,
-                              rsp, GmRope{}, sp, GmSide{}, pc);
-  else if (epi == GM_EPI_SWIGLU)
-    launch_gemm<GM_EPI_SWIGLU>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream), group_m,
-                               rsp, GmRope{}, sp, GmSide{}, pc);
-  else if (epi == GM_EPI_RESID)                    // C += A·Wᵀ in place (no row scales)
-    launch_gemm<GM_EPI_RESID>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream), group_m);
-  else if (epi == GM_EPI_RESID_LDS)                // the same, residual tile staged by DMA (A/B)
-    launch_gemm<GM_EPI_RESID_LDS>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream),
-                                  group_m, nullptr, GmRope{}, sp, GmSide{}, pc);
-  else if (epi == GM_EPI_RESID_PRE)                // ... with its first quarter prefetched at start (A/B)
-    launch_gemm<GM_EPI_RESID_PRE>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream),
-                                  group_m);
-  else if (epi == GM_EPI_STORE + 16)
-    launch_gemm<GM_EPI_STORE, true, 0>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream), group_m);
-  else if (epi == GM_EPI_STORE + 32)
-    launch_gemm<GM_EPI_STORE, false, 2>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream), group_m);
-  else if (epi == GM_EPI_SWIGLU + 48)
-    launch_gemm<GM_EPI_SWIGLU, true, 1>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream),
-                                        group_m, rsp);
-  else if (epi == GM_EPI_SWIGLU + 64)
-    launch_gemm<GM_EPI_SWIGLU, true, 3>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream),
-                                        group_m, rsp);
-  else if (epi == GM_EPI_SWIGLU + 80)
-    launch_gemm<GM_EPI_SWIGLU, true, 4>(P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, S(stream),
-                                        group_m, rsp);
-  else
-    throw std::invalid_argument("gemm: unknown epilogue");
   check_launch();
 }
 
@@ -334,42 +299,37 @@ static void gemm_qkv_rope(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr
                           uintptr_t cos_t, uintptr_t sin_t, int Hq, int Hkv, int max_ctx, int n_slots,
                           uintptr_t q, uintptr_t kc, uintptr_t vc, uintptr_t stream, uintptr_t rs,
                           int split_full, uintptr_t split_ws, uintptr_t split_cnt, int group_m) {
-  require(group_m >= 1 && group_m <= 64, "gemm_qkv_rope: group_m");
-  require(M > 0 && K > 0, "gemm_qkv_rope: empty operand");
+  check_gemm_operands("gemm_qkv_rope", a, w, 0, M, N, K, group_m, false);
   require(Hq % 2 == 0 && Hkv % 2 == 0 && Hkv >= 2, "gemm_qkv_rope: head counts must be even");
   require(N == (Hq + 2 * Hkv) * 128, "gemm_qkv_rope: N must be (Hq + 2 Hkv) * 128");
-  require(K % (2 * GM_BK) == 0, "gemm_qkv_rope: K must be a multiple of 128");
-  require((int64_t)M * K < (int64_t)1 << 30 && (int64_t)N * K < (int64_t)1 << 30, "gemm_qkv_rope: operand too large");
-  require(a % 16 == 0 && w % 16 == 0 && q % 16 == 0 && kc % 16 == 0 && vc % 16 == 0 && cos_t % 16 == 0 &&
-              sin_t % 16 == 0, "gemm_qkv_rope: pointers must be 16-byte aligned");
+  require(q % 16 == 0 && kc % 16 == 0 && vc % 16 == 0 && cos_t % 16 == 0 && sin_t % 16 == 0,
+          "gemm_qkv_rope: pointers must be 16-byte aligned");
   require(max_ctx > 0 && n_slots > 0, "gemm_qkv_rope: bad cache shape");
   GmRope rp{P<const int32_t>(pos), P<const int32_t>(slot), P<const float>(cos_t), P<const float>(sin_t),
             P<uint16_t>(q), P<uint16_t>(kc), P<uint16_t>(vc), Hq, Hkv, max_ctx, n_slots};
-  GmSplit sp{0, nullptr, nullptr};
-  if (split_ws) {
-    const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
-    require(split_full >= 0 && split_full < tiles, "gemm_qkv_rope: bad split");
-    require((K / GM_BK) % 4 == 0 && K / GM_BK >= 8, "gemm_qkv_rope: split-K needs K % 256 == 0 and K >= 512");
-    require(split_cnt != 0 && split_ws % 16 == 0, "gemm_qkv_rope: split workspace");
-    sp = GmSplit{split_full, P<float>(split_ws), P<int>(split_cnt)};
-  }
-  launch_gemm<GM_EPI_ROPE>(P<const uint16_t>(a), P<const uint16_t>(w), nullptr, M, N, K, S(stream), group_m,
-                           rs ? P<const float>(rs) : nullptr, rp, sp);
+  launch_gemm<GM_EPI_ROPE>(a, w, 0, M, N, K, stream, group_m, rs ? P<const float>(rs) : nullptr, rp,
+                           make_split("gemm_qkv_rope", M, N, K, split_full, split_ws, split_cnt));
+  check_launch();
+}
+
+// The LM head: the GEMM with EPI's per-tile (value, column) partials in pv /
+// pi [M][N / 256] (no [M][N] logits), then the reduction over the tiles to out [M].
+template <int EPI>
+static void launch_head(const char* fn, uintptr_t a, uintptr_t w, int M, int N, int K, const GmSide& side,
+                        uintptr_t out, uintptr_t stream) {
+  check_gemm_operands(fn, a, w, 0, M, N, K, GM_GROUP_M, false);
+  require_in(fn, (uintptr_t)side.pv % 4 == 0 && (uintptr_t)side.pi % 4 == 0 && out % 4 == 0, "alignment");
+  launch_gemm<EPI>(a, w, 0, M, N, K, stream, GM_GROUP_M, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, side);
+  hipLaunchKernelGGL(gemm_argmax_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, S(stream), side.pv, side.pi, M,
+                     N / GM_BN, P<int32_t>(out));
   check_launch();
 }
 
 // LM head + greedy sampling: out[m] = argmax_n (A[m] . W[n]) with the argmax
-// in the GEMM epilogue (no [M][N] logits); pv / pi: [M][N / 256] scratch.
+// in the GEMM epilogue (GM_EPI_ARGMAX).
 static void gemm_argmax(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr_t pv, uintptr_t pi,
                         uintptr_t out, uintptr_t stream) {
-  require(M > 0 && N % GM_BN == 0 && K % (2 * GM_BK) == 0, "gemm_argmax: M > 0, N % 256, K % 128");
-  require((int64_t)M * K < (1LL << 30) && (int64_t)N * K < (1LL << 30), "gemm_argmax: operand > 2 GiB");
-  require(a % 16 == 0 && w % 16 == 0 && pv % 4 == 0 && pi % 4 == 0 && out % 4 == 0, "gemm_argmax: alignment");
-  launch_gemm<GM_EPI_ARGMAX>(P<const uint16_t>(a), P<const uint16_t>(w), nullptr, M, N, K, S(stream), GM_GROUP_M,
-                             nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, GmSide{P<float>(pv), P<int32_t>(pi)});
-  hipLaunchKernelGGL(gemm_argmax_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, S(stream), P<const float>(pv),
-                     P<const int32_t>(pi), M, N / GM_BN, P<int32_t>(out));
-  check_launch();
+  launch_head<GM_EPI_ARGMAX>("gemm_argmax", a, w, M, N, K, GmSide{P<float>(pv), P<int32_t>(pi)}, out, stream);
 }
 
 // LM head + per-row temperature sampling: out[m] = argmax_n (A[m] . W[n] * inv_temp[m] + G(key[m], n)),
@@ -378,20 +338,14 @@ static void gemm_argmax(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr_t
 // [rows_padded] fp32 and key [rows_padded][2] uint32 hold whole 256-row tiles.
 static void gemm_sample(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr_t inv_temp, uintptr_t key,
                         int rows_padded, uintptr_t pv, uintptr_t pi, uintptr_t out, uintptr_t stream) {
-  require(M > 0 && N % GM_BN == 0 && K % (2 * GM_BK) == 0, "gemm_sample: M > 0, N % 256, K % 128");
-  require((int64_t)M * K < (1LL << 30) && (int64_t)N * K < (1LL << 30), "gemm_sample: operand > 2 GiB");
-  require(a % 16 == 0 && w % 16 == 0 && pv % 4 == 0 && pi % 4 == 0 && out % 4 == 0, "gemm_sample: alignment");
   require(inv_temp != 0 && key != 0 && inv_temp % 16 == 0 && key % 16 == 0,
           "gemm_sample: inv_temp / key must be 16-byte aligned");
-  require(rows_padded >= (M + GM_BM - 1) / GM_BM * GM_BM, "gemm_sample: inv_temp / key must hold whole 256-row tiles");
+  require(M > 0 && rows_padded >= (M + GM_BM - 1) / GM_BM * GM_BM,
+          "gemm_sample: inv_temp / key must hold whole 256-row tiles");
   GmSide side{P<float>(pv), P<int32_t>(pi)};
   side.inv_temp = P<const float>(inv_temp);
   side.key = P<const uint32_t>(key);
-  launch_gemm<GM_EPI_SAMPLE>(P<const uint16_t>(a), P<const uint16_t>(w), nullptr, M, N, K, S(stream), GM_GROUP_M,
-                             nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, side);
-  hipLaunchKernelGGL(gemm_argmax_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, S(stream), P<const float>(pv),
-                     P<const int32_t>(pi), M, N / GM_BN, P<int32_t>(out));
-  check_launch();
+  launch_head<GM_EPI_SAMPLE>("gemm_sample", a, w, M, N, K, side, out, stream);
 }
 
 // out[k][i] = noise bits of column n0 + i under keys[k] = (k0, k1): the device generator, for tests

@@ -1,15 +1,17 @@
-"""Hand-written gfx950 GEMMs (``csrc/kernels/gemm_kernels.h``).
+"""Hand-written gfx950 GEMMs (``csrc/kernels/gemm_kernels.h``, ``skinny_kernels.h``).
 
-``gemm_swiglu(x, w_perm)`` computes the Llama MLP's ``silu(x·Wgᵀ) * (x·Wuᵀ)``
-in ONE launch: the gate/up product never reaches HBM and the separate
-``silu_mul`` pass disappears.  ``w_perm`` is the [2F][K] gate/up weight with
-its rows permuted by :func:`swiglu_permute` so that, inside every 256-column
-output tile, each wave's 64 columns are 32 gate features followed by the same
-32 up features (the kernel's register layout puts g and u of one element in
-the same lane).  ``gemm(x, w)`` is the plain ``x·Wᵀ`` on the same kernel,
-kept for A/B measurements against hipBLASLt.  ``qkv_rope`` runs the qkv
-projection with the RoPE + K/V-cache-write epilogue (replacing F.linear +
-``rope_kv``).
+The 256x256-tile kernel, one launch per call, by epilogue: ``gemm`` (plain
+``x·Wᵀ``), ``gemm_swiglu`` (the Llama MLP's ``silu(x·Wgᵀ) * (x·Wuᵀ)`` over a
+:func:`swiglu_permute`-d weight: inside every 256-column tile each wave's 64
+columns are 32 gate features then the same 32 up features, so g and u of one
+element share a lane and the gate/up product never reaches HBM), ``qkv_rope``
+(qkv projection + RoPE + K/V-cache write), ``gemm_residual`` /
+``gemm_residual_rms`` (``res += x·Wᵀ`` in place, the second with the next
+RMSNorm's row scales) and ``lm_head_argmax`` / ``lm_head_sample`` (the LM head
+with greedy or per-row temperature sampling, no logits tensor).  The first
+three take ``row_scale`` (the folded RMSNorm).  A step too small to fill the
+CUs runs split-K (:func:`split_plan`, :func:`split_all`) or, below
+``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`).
 
 CPU / reference path: :func:`swiglu_reference` (fp32 math of the same op).
 """
@@ -28,6 +30,7 @@ EPI_RESID_LDS = 6   # residual tile staged into LDS by DMA, added in place (defa
 EPI_RESID_PRE = 7   # A/B: ... its first quarter fetched into spare LDS at kernel start
 # which residual epilogue ``gemm_residual`` launches (bench.py --resid-epi)
 RESID_EPI = EPI_RESID_LDS
+TILE_M = 256
 TILE_N = 256
 SWIGLU_HALF = 32   # per-wave gate/up split (a wave owns 64 output columns)
 
@@ -82,6 +85,10 @@ def supported(M: int, N: int, K: int) -> bool:
     return M > 0 and N % TILE_N == 0 and K % 128 == 0
 
 
+def _tiles(M: int, N: int) -> int:
+    return (M + TILE_M - 1) // TILE_M * (N // TILE_N)
+
+
 def row_scale_len(M: int) -> int:
     """Floats a row_scale buffer must hold: the kernel reads whole 256-row
     tiles of it (rows past M are read but never stored)."""
@@ -103,7 +110,7 @@ def split_all(M: int, N: int, K: int, cus: int):
     """Split-K for a step too small to fill ``cus`` CUs with whole tiles:
     every tile runs as two K-half blocks (returns 0 = the first whole
     tile index) when twice the tiles still fit one wave, else None."""
-    tiles = (M + TILE_M - 1) // TILE_M * (N // TILE_N)
+    tiles = _tiles(M, N)
     if cus <= 0 or 2 * tiles > cus or K % 256 or K < 512:
         return None
     return 0
@@ -125,7 +132,7 @@ def _launch(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, group
         f = split_plan(M, N, K, split_cus) if f is None else f
     ws = cnt = 0
     if f is not None:
-        n_split = (M + TILE_M - 1) // TILE_M * (N // TILE_N) - f
+        n_split = _tiles(M, N) - f
         w_t, c_t = _split_workspace(x.device, stream, n_split, max(split_cus, 2 * n_split))
         ws, cnt = w_t.data_ptr(), c_t.data_ptr()
     k.gemm_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, epi, stream, group_m,
@@ -229,12 +236,11 @@ def residual_tiles_ok(M: int, N: int, cus: int, min_fill: float = 0.97) -> bool:
     the idle CUs and stays ahead (profiles/r2_gemm_resid_ab.jsonl)."""
     if not supported(M, N, 128) or N % TILE_N:
         return False
-    tiles = -(-M // TILE_M) * (N // TILE_N)
+    tiles = _tiles(M, N)
     waves = -(-tiles // cus)
     return tiles / (waves * cus) >= min_fill
 
 
-TILE_M = 256
 _SPLIT_WS = {}
 
 
@@ -245,7 +251,7 @@ def split_plan(M: int, N: int, K: int, cus: int):
     full its tiles run as two blocks over one K-half each (one wave of
     ``cus`` becomes half a wave).  qkv at the serving shape: 16 x 24 = 384
     tiles on 256 CUs -> 256 whole + 128 split."""
-    tiles = (M + TILE_M - 1) // TILE_M * (N // TILE_N)
+    tiles = _tiles(M, N)
     tail = tiles % cus
     if tiles <= cus or tail == 0 or 2 * tail > cus or K % 256 or K < 512:
         return None
@@ -320,7 +326,7 @@ def qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, pos: torch.Tensor, slot: torch
         cus = _cu_count(x.device)
         f = split_plan(T, N, K, cus) if split_full is None else split_full
         if f is not None:
-            n_split = (T + TILE_M - 1) // TILE_M * (N // TILE_N) - f
+            n_split = _tiles(T, N) - f
             w_t, c_t = _split_workspace(x.device, stream, n_split, cus)
             full, ws, cnt = f, w_t.data_ptr(), c_t.data_ptr()
     k.gemm_qkv_rope(x.data_ptr(), wqkv.data_ptr(), T, N, K, pos.data_ptr(), slot.data_ptr(),
@@ -393,6 +399,31 @@ def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_sc
 _ARGMAX_WS = {}
 
 
+def _head_scratch(device, stream: int, M: int, N: int):
+    """Per-(device, stream) [M][N/256] (value, column) partials, grown by doubling."""
+    key = (device.type, device.index, stream)
+    ws = _ARGMAX_WS.get(key)
+    if ws is None or ws[0].numel() < M * (N // TILE_N):
+        n = max(M * (N // TILE_N), 2 * ws[0].numel() if ws is not None else 0)
+        ws = _ARGMAX_WS[key] = (torch.empty(n, dtype=torch.float32, device=device),
+                                torch.empty(n, dtype=torch.int32, device=device))
+    return ws
+
+
+def _head_args(fn: str, x: torch.Tensor, w: torch.Tensor, out):   # checks, scratch, the int32 [M] output
+    _check(x, "x")
+    _check(w, "w")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or not supported(M, N, K):
+        raise ValueError(f"{fn}: unsupported shape M={M} N={N} K={K}")
+    y = out if out is not None else torch.empty(M, dtype=torch.int32, device=x.device)
+    if y.dtype != torch.int32 or y.numel() < M or not y.is_contiguous():
+        raise ValueError(f"{fn}: out must be contiguous int32 [M]")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    return M, N, K, stream, _head_scratch(x.device, stream, M, N), y
+
+
 def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """Greedy next tokens ``argmax_n (x . w[n])`` -> int32 [M] with the argmax
     in the GEMM epilogue: no [M][vocab] logits tensor is written or re-read
@@ -400,23 +431,7 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor = None) -
     to the lower index as torch.argmax does; the values compared are the fp32
     accumulators, not bf16-rounded logits.  Scratch [M][N/256] (value, column)
     partials are cached per (device, stream)."""
-    _check(x, "x")
-    _check(w, "w")
-    M, K = x.shape
-    N = w.shape[0]
-    if w.shape[1] != K or not supported(M, N, K):
-        raise ValueError(f"lm_head_argmax: unsupported shape M={M} N={N} K={K}")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device.type, x.device.index, stream)
-    need = M * (N // TILE_N)
-    ws = _ARGMAX_WS.get(key)
-    if ws is None or ws[0].numel() < need:
-        n = max(need, 2 * ws[0].numel() if ws is not None else 0)
-        ws = _ARGMAX_WS[key] = (torch.empty(n, dtype=torch.float32, device=x.device),
-                                torch.empty(n, dtype=torch.int32, device=x.device))
-    y = out if out is not None else torch.empty(M, dtype=torch.int32, device=x.device)
-    if y.dtype != torch.int32 or y.numel() < M or not y.is_contiguous():
-        raise ValueError("lm_head_argmax: out must be contiguous int32 [M]")
+    M, N, K, stream, ws, y = _head_args("lm_head_argmax", x, w, out)
     _native.require_hipops().gemm_argmax(x.data_ptr(), w.data_ptr(), M, N, K, ws[0].data_ptr(), ws[1].data_ptr(),
                                          y.data_ptr(), stream)
     return y
@@ -433,12 +448,7 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, inv_temp: torch.Tensor, key
     ``ops.sampling.row_keys``.  The kernel reads whole 256-row tiles of both:
     pass them ``row_scale_len(M)`` rows long (rows past M zero) or they are
     padded here.  Shares ``lm_head_argmax``'s scratch."""
-    _check(x, "x")
-    _check(w, "w")
-    M, K = x.shape
-    N = w.shape[0]
-    if w.shape[1] != K or not supported(M, N, K):
-        raise ValueError(f"lm_head_sample: unsupported shape M={M} N={N} K={K}")
+    M, N, K, stream, ws, y = _head_args("lm_head_sample", x, w, out)
     if inv_temp.dtype != torch.float32 or inv_temp.dim() != 1 or inv_temp.numel() < M or inv_temp.device != x.device:
         raise ValueError("lm_head_sample: inv_temp must be float32 [>= M] on x's device")
     if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 2 or keys.shape[1] != 2 \
@@ -449,17 +459,6 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, inv_temp: torch.Tensor, key
         inv_temp = torch.nn.functional.pad(inv_temp[:M], (0, Mp - M))
     if keys.shape[0] < Mp or not keys.is_contiguous() or keys.data_ptr() % 16:
         keys = torch.nn.functional.pad(keys[:M].view(torch.int32), (0, 0, 0, Mp - M))
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device.type, x.device.index, stream)
-    need = M * (N // TILE_N)
-    ws = _ARGMAX_WS.get(key)
-    if ws is None or ws[0].numel() < need:
-        n = max(need, 2 * ws[0].numel() if ws is not None else 0)
-        ws = _ARGMAX_WS[key] = (torch.empty(n, dtype=torch.float32, device=x.device),
-                                torch.empty(n, dtype=torch.int32, device=x.device))
-    y = out if out is not None else torch.empty(M, dtype=torch.int32, device=x.device)
-    if y.dtype != torch.int32 or y.numel() < M or not y.is_contiguous():
-        raise ValueError("lm_head_sample: out must be contiguous int32 [M]")
     _native.require_hipops().gemm_sample(x.data_ptr(), w.data_ptr(), M, N, K, inv_temp.data_ptr(), keys.data_ptr(),
                                          Mp, ws[0].data_ptr(), ws[1].data_ptr(), y.data_ptr(), stream)
     return y

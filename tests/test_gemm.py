@@ -260,6 +260,22 @@ def test_gemm_residual_matches_fp32(T, K, epi):
 
 
 @pytest.mark.gpu
+def test_gemm_bf16_rejects_retired_codes_and_a_row_scale_on_the_residual():
+    """The retired A/B epilogue codes (round-1 schedule, no stagger, the
+    s_setprio variants, the persistent-grid flag) and a row scale with
+    EPI_RESID, which the kernel would ignore, raise before any launch."""
+    x, w = _rand(1, 128, 256)
+    out = torch.full((1, 256), 3.0, dtype=torch.bfloat16, device=DEV)
+    for code in (16, 32, 50, 66, 82, 0 | 256):
+        with pytest.raises(ValueError):
+            G._launch(x, w, out, code)
+    with pytest.raises(ValueError):
+        G._launch(x, w, out, G.EPI_RESID, row_scale=torch.ones(256, device=DEV))
+    torch.cuda.synchronize()
+    assert (out == 3.0).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("T,K", [(37, 4096), (300, 1024), (4041, 4096), (4096, 14336)])
 def test_gemm_residual_rms_matches_row_rms(T, K):
     """The residual GEMM with the fused RMSNorm row scale: ``res`` exactly as

@@ -61,13 +61,18 @@ def release_streams() -> None:
     allocated on them can be freed later: the caller dropped every engine
     and tensor first.  The GPU is drained and the allocator's cached blocks
     released before the streams go (a profiler's exit-time teardown then
-    finds no live external stream)."""
+    finds no live external stream).  The GEMM scratch cached for these
+    streams (``ops.gemm``) is forgotten first, so it is freed here too."""
     if not _STREAMS:
         return
     import gc
 
     import torch
     from .. import _native
+    from ..ops.gemm import drop_stream_scratch
+    for big, micro, _n in _STREAMS.values():
+        drop_stream_scratch(big.cuda_stream)
+        drop_stream_scratch(micro.cuda_stream)
     gc.collect()
     torch.cuda.synchronize()
     torch.cuda.empty_cache()

@@ -93,8 +93,8 @@ class StepResult:
 
 
 class _blas:
-    """torch's library-GEMM backend for a block ("cublas" = rocBLAS on ROCm,
-    "cublaslt" = hipBLASLt), restored after it (the serve loop is one thread)."""
+    """torch's library-GEMM backend for a block (``cublas`` = rocBLAS on ROCm,
+    ``cublaslt`` = hipBLASLt), restored after it (the serve loop is one thread)."""
 
     def __init__(self, lib: str):
         self.lib = lib
@@ -793,14 +793,8 @@ class BackendEngine:
                     tiles = torch.stack([r, torch.ones_like(r), slot, pos], 1).contiguous() \
                         if self.use_tiles else None
                     samp = torch.arange(min(T, self.micro_slots), device=dev, dtype=torch.long)
-                    if self.micro_cus and self.micro_gemm == "rocblas":
-                        with _blas("cublas"):
-                            self.model.forward(torch.zeros(T, dtype=torch.long, device=dev), pos.contiguous(),
-                                               slot.contiguous(), samp, tiles=tiles, n_dec=0)
-                    else:
-                        self.model.forward(torch.zeros(T, dtype=torch.long, device=dev), pos.contiguous(),
-                                           slot.contiguous(), samp, tiles=tiles, n_dec=0,
-                                           **({"small_cus": self.micro_cus} if self.micro_cus else {}))
+                    self._micro_forward(torch.zeros(T, dtype=torch.long, device=dev), pos.contiguous(),
+                                        slot.contiguous(), samp, tiles, 0)
                     n += 1
                     T *= 2
         if self.micro_graph:
@@ -845,39 +839,21 @@ class BackendEngine:
             self.host_ns[2] += time.perf_counter_ns() - te
             host_out[:D].copy_(out[:D], non_blocking=True)
             ev = self._end_event(D, ev0 is not None)
-        # the same deterministic bookkeeping as an eager micro-forward
-        ss = samp_slots
-        gidx = self.s_gen[ss].copy()
-        self.s_gen[ss] += 1
-        self.s_out_idx[ss] = np.arange(len(ss))
-        self.s_out_step[ss] = sid
-        g = self.s_gen[ss]
-        firsts = [self.active[int(x)] for x in ss[g == 1]]
-        done = ss[g >= self.s_gmax[ss]]
-        completed = []
-        for x in done.tolist():
-            r = self.active.pop(x)
-            r.prefilled = int(self.s_plen[x]) - r.reused
-            r.generated = int(self.s_gen[x])
-            completed.append(r)
-            self.s_conv[x] = -1
-            self.free_micro.append(x)
-        self.s_active[done] = False
-        f = _Inflight(sid, ev, D, 0, D, completed, firsts, t0, out, t_mono, ev0, micro=True,
-                      samp_slots=ss, gidx=gidx, host_out=host_out)
-        self._prev_out_m = out
-        self._qm.append(f)
-        self.micro_id += 1
-        self.micro_steps += 1
-        self.micro_graph_steps += 1
-        self.total_tokens += D
-        self.matmul_flops += self._step_flops(D, D)
-        self.completed_total += len(completed)
-        self.completed_tokens += sum(len(r.prompt) + r.gen_tokens - 1 for r in completed)
-        return True
+        return self._retire(sid, D, 0, D, D, samp_slots, out, host_out, ev, ev0, t0, t_mono, True, graph=True)
 
-    def _micro_forward_kw(self) -> dict:
-        return {"small_cus": self.micro_cus} if self.micro_cus else {}
+    def _micro_forward(self, tok, pos, slot, samp, tiles, n_dec: int, graph: bool = False, **skw):
+        """Issue one micro-forward on the current stream: the model's small
+        GEMMs sized for ``micro_cus`` CUs, or, with ``micro_gemm = "rocblas"``,
+        rocBLAS.  ``rocblas`` applies to eager micro-forwards only: the
+        captured graphs (``graph``: the capture and its two warm-ups) always
+        hold the hand-written kernels, so graph-replayed decode steps run
+        those whatever ``micro_gemm`` says."""
+        if self.micro_cus and self.micro_gemm == "rocblas" and not graph:
+            with _blas("cublas"):
+                return self.model.forward(tok, pos, slot, samp, tiles=tiles, n_dec=n_dec, **skw)
+        if self.micro_cus:
+            skw["small_cus"] = self.micro_cus
+        return self.model.forward(tok, pos, slot, samp, tiles=tiles, n_dec=n_dec, **skw)
 
     def _capture_micro_graphs(self) -> int:
         """Capture the decode-only micro-forward once per row bucket on the
@@ -901,15 +877,14 @@ class BackendEngine:
             til[:, 1] = 1
             til[:, 2] = self.scratch_slot
             samp = torch.arange(Tb, device=dev, dtype=torch.long)
-            kw = self._micro_forward_kw()
             torch.cuda.synchronize(dev)
             with torch.cuda.stream(rt):
                 for _ in range(2):
-                    self.model.forward(g_tok, pos, slot, samp, tiles=til, n_dec=Tb, **kw)
+                    self._micro_forward(g_tok, pos, slot, samp, til, Tb, graph=True)
             torch.cuda.synchronize(dev)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, pool=pool, stream=rt, capture_error_mode="thread_local"):
-                out = self.model.forward(g_tok, pos, slot, samp, tiles=til, n_dec=Tb, **kw)
+                out = self._micro_forward(g_tok, pos, slot, samp, til, Tb, graph=True)
             torch.cuda.synchronize(dev)
             self._mg[Tb] = (graph, g_in, g_tok, out)
             n += 1
@@ -1087,23 +1062,22 @@ class BackendEngine:
                 self.sampled_steps += 1
             ev0 = self._start_event()
             te = time.perf_counter_ns()
-            if micro and self.micro_cus and self.micro_gemm == "rocblas":
-                with _blas("cublas"):
-                    out = self.model.forward(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til,
-                                             n_dec=D, **skw)
-            else:
-                out = self.model.forward(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til,
-                                         n_dec=D,
-                                         **({"small_cus": self.micro_cus} if micro and self.micro_cus else {}),
-                                         **skw)
+            fwd = self._micro_forward if micro else self.model.forward
+            out = fwd(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til, n_dec=D, **skw)
             self.host_ns[2] += time.perf_counter_ns() - te
             if not micro:
                 self._census(T)
             # the sampled ids come back behind the forward (read at reap)
             host_out[:S].copy_(out, non_blocking=True)
             ev = self._end_event(T, ev0 is not None)
-        # deterministic bookkeeping: every sampled slot gets one token
-        ss = samp_slots
+        return self._retire(sid, T, n_pre, n_dec, S, samp_slots, out, host_out, ev, ev0, t0, t_mono, micro)
+
+    def _retire(self, sid: int, T: int, n_pre: int, n_dec: int, S: int, ss, out, host_out, ev, ev0,
+                t0: float, t_mono: int, micro: bool, graph: bool = False) -> bool:
+        """The deterministic bookkeeping behind every enqueued forward (a
+        serving step, an eager micro-forward or a graph replay): every sampled
+        slot gets one token, finished requests leave their slots, and the
+        step joins its pool's in-flight queue."""
         gidx = self.s_gen[ss].copy()
         self.s_gen[ss] += 1
         self.s_out_idx[ss] = np.arange(len(ss))
@@ -1118,6 +1092,7 @@ class BackendEngine:
             r.generated = int(self.s_gen[x])
             completed.append(r)
             if micro:
+                # a micro slot never parks dialog KV (conv_lru holds serving slots only): always freed
                 self.s_conv[x] = -1
                 self.free_micro.append(x)
             elif r.conv >= 0:
@@ -1139,6 +1114,7 @@ class BackendEngine:
             self._qm.append(f)
             self.micro_id += 1
             self.micro_steps += 1
+            self.micro_graph_steps += int(graph)
         else:
             self._prev_out = out
             self._q.append(f)

@@ -106,6 +106,51 @@ def _row_scale_ptr(rs, M: int) -> int:
     return rs.data_ptr()
 
 
+_SCRATCH = {}   # (device type, device index, stream handle, user) -> (live tensors, retired tensors)
+
+
+def _scratch_entry(device, stream: int, name: str):
+    """The (live, retired) tensor lists of user ``name`` on one stream."""
+    key = (device.type, device.index, stream, name)
+    entry = _SCRATCH.get(key)
+    if entry is None:
+        entry = _SCRATCH[key] = ([], [])
+    return entry
+
+
+def _scratch(device, stream: int, name: str, *specs):
+    """The kernels' grow-only scratch, one entry per (device, stream) and user
+    ("split", "rms", "skinny", "head"): the entry's tensors, one per
+    ``(need, floor, alloc, dtype)`` in ``specs``.  A tensor of at least
+    ``need`` elements is returned as it is, so launches in stream order share
+    it and concurrent streams never do.  One too small is replaced by
+    ``alloc`` (``torch.zeros`` for the counters the kernels find and leave
+    zero, else ``torch.empty``) of ``max(need, floor, 2 * old)`` elements and
+    moves to the entry's retired list, where it lives until
+    :func:`drop_stream_scratch`: a captured graph or a launch in flight may
+    still point at it, so the allocator must not hand it to anyone else.
+    Growth at least doubles, which keeps the retired tensors together
+    smaller than the live one."""
+    live, retired = _SCRATCH.get((device.type, device.index, stream, name)) or _scratch_entry(device, stream, name)
+    if not live:
+        live.extend(alloc(max(need, floor), dtype=dtype, device=device) for need, floor, alloc, dtype in specs)
+    for i, (need, floor, alloc, dtype) in enumerate(specs):
+        old = live[i]
+        if old.numel() < need:
+            live[i] = alloc(max(need, floor, 2 * old.numel()), dtype=dtype, device=device)
+            retired.append(old)
+    return live
+
+
+def drop_stream_scratch(stream: int) -> None:
+    """Forget every scratch tensor, live and retired, of stream handle
+    ``stream`` on any device (before the stream is destroyed: nothing that
+    was allocated on it may be freed after, and a new stream reusing the
+    handle must not inherit them)."""
+    for key in [k for k in _SCRATCH if k[2] == stream]:
+        del _SCRATCH[key]
+
+
 def split_all(M: int, N: int, K: int, cus: int):
     """Split-K for a step too small to fill ``cus`` CUs with whole tiles:
     every tile runs as two K-half blocks (returns 0 = the first whole
@@ -169,21 +214,12 @@ def gemm_swiglu(x: torch.Tensor, w_perm: torch.Tensor, out: torch.Tensor = None,
     return _launch(x, w_perm, y, EPI_SWIGLU, row_scale=row_scale, split_cus=split_cus)
 
 
-_RMS_WS = {}
-
-
 def _rms_workspace(device, stream: int, tiles_m: int, tiles_n: int):
-    """Per-(device, stream) scratch of the fused row-scale epilogue: fp32
-    row partials [tiles_m * tiles_n * 256] and int tickets [tiles_m] (zero;
-    every launch leaves them zero), grown on demand."""
-    key = (device.type, device.index, stream)
-    ws = _RMS_WS.get(key)
-    if ws is None or ws[0].numel() < tiles_m * tiles_n * 256 or ws[1].numel() < tiles_m:
-        tm = max(tiles_m, ws[1].numel() if ws else 0)
-        ws = (torch.empty(tm * max(tiles_n, 16) * 256, dtype=torch.float32, device=device),
-              torch.zeros(tm, dtype=torch.int32, device=device))
-        _RMS_WS[key] = ws
-    return ws
+    """Scratch of the fused row-scale epilogue: fp32 row partials [tiles_m *
+    tiles_n * 256] and int tickets [tiles_m] (zero; every launch leaves them zero)."""
+    return _scratch(device, stream, "rms",
+                    (tiles_m * tiles_n * 256, tiles_m * max(tiles_n, 16) * 256, torch.empty, torch.float32),
+                    (tiles_m, 0, torch.zeros, torch.int32))
 
 
 def gemm_residual_rms(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, eps: float) -> torch.Tensor:
@@ -241,9 +277,6 @@ def residual_tiles_ok(M: int, N: int, cus: int, min_fill: float = 0.97) -> bool:
     return tiles / (waves * cus) >= min_fill
 
 
-_SPLIT_WS = {}
-
-
 def split_plan(M: int, N: int, K: int, cus: int):
     """Split-K for the last, partial wave of tiles: returns ``full`` (tiles
     run whole) or None.  The kernel holds one block per CU, so ``tiles`` over
@@ -261,18 +294,10 @@ def split_plan(M: int, N: int, K: int, cus: int):
 def _split_workspace(device, stream: int, n_split: int, cus: int):
     """fp32 slabs (256 KiB per split tile) + zeroed ticket/ready counters,
     sized for the largest possible tail (cus / 2).  The kernel re-zeroes the
-    counters it used, so launches in stream order can share them; the cache
-    is keyed by (device, stream) so concurrent streams never do."""
-    key = (device.type, device.index, stream)
-    ws = _SPLIT_WS.get(key)
-    if ws is None or n_split > ws[1].numel() // 2:
-        # (grown in stream order: a launch still using the old slabs is ahead
-        # on this same stream, and the caching allocator reuses them after it)
-        cap = max(cus // 2, n_split, ws[1].numel() // 2 if ws is not None else 0)
-        ws = (torch.empty(cap * 512 * 128, dtype=torch.float32, device=device),
-              torch.zeros(cap * 2, dtype=torch.int32, device=device))
-        _SPLIT_WS[key] = ws
-    return ws
+    counters it used, so launches in stream order can share them."""
+    cap = max(cus // 2, n_split)
+    return _scratch(device, stream, "split", (n_split * 512 * 128, cap * 512 * 128, torch.empty, torch.float32),
+                    (n_split * 2, cap * 2, torch.zeros, torch.int32))
 
 
 @functools.lru_cache(maxsize=None)
@@ -341,7 +366,6 @@ SKINNY_PROJ_MAX_M = 256        # ... and qkv up to this many (profiles/r6_skinny
 SKINNY_RESID_MAX_M = 512       # ... and o / down (into the residual) up to this many (profiles/r6_skinny_mid_m.jsonl)
 SKINNY_CHUNKED_MAX_M = 1024    # the kernel itself: 128-row chunks of A up to this many rows
 SK_STORE, SK_RESID, SK_SWIGLU = 0, 1, 2
-_SKINNY_WS = {}
 
 
 def skinny_splits(N: int, K: int, cus: int, M: int = 1) -> int:
@@ -381,11 +405,7 @@ def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_sc
     if K % (128 * S):
         raise ValueError(f"skinny: K={K} does not split {S} ways in 128-deep steps")
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device.type, x.device.index, stream)
-    need = S * M * N
-    ws = _SKINNY_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _SKINNY_WS[key] = torch.empty(max(need, SKINNY_MAX_M * 32768), dtype=torch.float32, device=x.device)
+    ws, = _scratch(x.device, stream, "skinny", (S * M * N, SKINNY_MAX_M * 32768, torch.empty, torch.float32))
     rs = 0
     if row_scale is not None:
         if row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or row_scale.numel() < M:
@@ -396,18 +416,10 @@ def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_sc
     return out
 
 
-_ARGMAX_WS = {}
-
-
 def _head_scratch(device, stream: int, M: int, N: int):
-    """Per-(device, stream) [M][N/256] (value, column) partials, grown by doubling."""
-    key = (device.type, device.index, stream)
-    ws = _ARGMAX_WS.get(key)
-    if ws is None or ws[0].numel() < M * (N // TILE_N):
-        n = max(M * (N // TILE_N), 2 * ws[0].numel() if ws is not None else 0)
-        ws = _ARGMAX_WS[key] = (torch.empty(n, dtype=torch.float32, device=device),
-                                torch.empty(n, dtype=torch.int32, device=device))
-    return ws
+    """[M][N/256] (value, column) partials of the LM-head epilogues."""
+    n = M * (N // TILE_N)
+    return _scratch(device, stream, "head", (n, 0, torch.empty, torch.float32), (n, 0, torch.empty, torch.int32))
 
 
 def _head_args(fn: str, x: torch.Tensor, w: torch.Tensor, out):   # checks, scratch, the int32 [M] output

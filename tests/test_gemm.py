@@ -1,10 +1,14 @@
 """Hand-written gfx950 GEMM (csrc/kernels/gemm_kernels.h, ops/gemm.py).
 
-CPU: the swiglu weight permutation and the model's fused-MLP reference path.
+CPU: the swiglu weight permutation, the model's fused-MLP reference path and
+the grow-only scratch cache (driven with CPU tensors and made-up stream handles).
 GPU: the kernel against fp32 PyTorch references at T in {1, 37, 300, 4096}
 (4096: the serving step), plain and SwiGLU epilogues, the permuted silu_mul,
 and a tiny model forward with the fused MLP against the ref ops.
 """
+import gc
+import weakref
+
 import pytest
 import torch
 
@@ -94,6 +98,70 @@ def test_gemm_rejects_unsupported_shapes():
     assert not G.supported(37, 500, 256)
     assert not G.supported(37, 512, 200)
     assert not G.supported(0, 512, 256)
+
+
+CPU = torch.device("cpu")
+
+
+@pytest.fixture
+def scratch_handles():
+    """Made-up stream handles 1 and 2 of the scratch cache, dropped afterwards."""
+    yield 1, 2
+    G.drop_stream_scratch(1)
+    G.drop_stream_scratch(2)
+
+
+def _floats(need, floor=0):
+    return need, floor, torch.empty, torch.float32
+
+
+def test_scratch_growth_keeps_the_old_buffer(scratch_handles):
+    h, _ = scratch_handles
+    a, = G._scratch(CPU, h, "skinny", _floats(100, 256))
+    n_a, ptr_a, alive = a.numel(), a.data_ptr(), weakref.ref(a)
+    assert n_a == 256                                          # the user's minimum size
+    del a
+    b, = G._scratch(CPU, h, "skinny", _floats(n_a + 1, 256))
+    assert b.numel() >= 2 * n_a and b.data_ptr() != ptr_a      # growth at least doubles
+    gc.collect()
+    live, retired = G._scratch_entry(CPU, h, "skinny")
+    assert alive() is not None and [t.data_ptr() for t in retired] == [ptr_a]
+    assert live[0] is b
+    c, = G._scratch(CPU, h, "skinny", _floats(b.numel(), 256))   # fits: the very same tensor
+    assert c is b and len(retired) == 1
+
+
+def test_scratch_counters_are_zero_and_meet_the_minimum_sizes(scratch_handles):
+    h, _ = scratch_handles
+    slab, cnt = G._split_workspace(CPU, h, 3, 16)              # max(cus // 2, n_split) = 8 tiles
+    assert slab.numel() == 8 * 512 * 128 and cnt.numel() == 8 * 2 and int(cnt.abs().sum()) == 0
+    cnt.fill_(7)                                               # (a replacement must not copy this)
+    slab2, cnt2 = G._split_workspace(CPU, h, 9, 16)
+    assert slab2.numel() >= 2 * slab.numel() and cnt2.numel() >= 2 * cnt.numel() and cnt2.numel() >= 9 * 2
+    assert int(cnt2.abs().sum()) == 0
+    part, tick = G._rms_workspace(CPU, h, 2, 4)                # max(tiles_n, 16) column tiles
+    assert part.numel() == 2 * 16 * 256 and tick.numel() == 2 and int(tick.abs().sum()) == 0
+    tick.fill_(7)
+    part2, tick2 = G._rms_workspace(CPU, h, 5, 4)              # more row tiles: the tickets grow
+    assert tick2.numel() >= 5 and int(tick2.abs().sum()) == 0 and part2.numel() >= 5 * 4 * 256
+    val, col = G._head_scratch(CPU, h, 3, 1024)
+    assert val.numel() == col.numel() == 3 * 4 and (val.dtype, col.dtype) == (torch.float32, torch.int32)
+
+
+def test_drop_stream_scratch_is_per_stream(scratch_handles):
+    h1, h2 = scratch_handles
+    a, = G._scratch(CPU, h1, "skinny", _floats(64))
+    G._scratch(CPU, h1, "skinny", _floats(65))                  # a is retired
+    G._split_workspace(CPU, h1, 1, 4)
+    keep = [G._scratch(CPU, h2, "skinny", _floats(64))[0], *G._split_workspace(CPU, h2, 1, 4)]
+    alive = weakref.ref(a)
+    del a
+    G.drop_stream_scratch(h1)
+    gc.collect()
+    assert alive() is None
+    assert G._scratch_entry(CPU, h1, "skinny") == ([], []) and G._scratch_entry(CPU, h1, "split") == ([], [])
+    assert G._scratch(CPU, h2, "skinny", _floats(64))[0] is keep[0]
+    assert all(x is y for x, y in zip(G._split_workspace(CPU, h2, 1, 4), keep[1:]))
 
 
 # ----------------------------------------------------------------------------- GPU
@@ -411,7 +479,7 @@ def test_qkv_rope_split_k_tail_matches_unsplit(T):
         assert (q1.float() - q2.float()).abs().max().item() <= tol, it
         assert (kc1.float() - kc2.float()).abs().max().item() <= tol, it
         assert (vc1.float() - vc2.float()).abs().max().item() <= tol, it
-    _, cnt = G._SPLIT_WS[("cuda", 0, torch.cuda.current_stream().cuda_stream)]
+    _, cnt = G._scratch_entry(x.device, torch.cuda.current_stream().cuda_stream, "split")[0]
     assert int(cnt.abs().sum()) == 0                             # left zeroed for the next launch
 
 
@@ -578,6 +646,46 @@ def test_skinny_swiglu_matches_fp32(M):
     out = torch.empty(M, 1536, dtype=torch.bfloat16, device=DEV)
     G.skinny(x, G.swiglu_permute(w), out, G.SK_SWIGLU, row_scale=r, cus=32)
     assert (out.float() - ref).abs().max().item() <= 0.02 * ref.abs().max().item() + 1e-3
+
+
+@pytest.mark.gpu
+def test_replayed_graph_survives_skinny_scratch_growth():
+    """A graph captured over the stream's skinny scratch keeps its buffer
+    when a later, larger eager call on that stream replaces it: the old
+    buffer is retired, not freed, so a tensor allocated afterwards (filled
+    with NaN here) cannot land in the block the replay writes and reads."""
+    s = torch.cuda.Stream()
+    x, w = _rand(8, 2048, 2048, seed=77)
+    out = torch.empty(8, 2048, dtype=torch.bfloat16, device=DEV)
+    xb, wb = _rand(1024, 2048, 4096, seed=78)
+    outb = torch.empty(1024, 4096, dtype=torch.bfloat16, device=DEV)
+    graph = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    try:
+        with torch.cuda.stream(s):
+            G.skinny(x, w, out, G.SK_STORE)                       # the 2 Mi-float minimum buffer
+        s.synchronize()
+        live, retired = G._scratch_entry(x.device, s.cuda_stream, "skinny")
+        old = live[0]
+        assert old.numel() == G.SKINNY_MAX_M * 32768 and not retired
+        with torch.cuda.graph(graph, stream=s):
+            G.skinny(x, w, out, G.SK_STORE)
+        assert live[0] is old                                     # (the capture used the cached buffer)
+        with torch.cuda.stream(s):
+            graph.replay()
+            first = out.clone()
+            G.skinny(xb, wb, outb, G.SK_STORE)                    # S * M * N = 4 Mi floats: the scratch grows
+            poison = torch.full((old.numel(),), float("nan"), dtype=torch.float32, device=DEV)
+            out.zero_()
+            graph.replay()
+        s.synchronize()
+        assert live[0] is not old and live[0].numel() >= 2 * old.numel()
+        assert [t.data_ptr() for t in retired] == [old.data_ptr()]
+        assert poison.data_ptr() != old.data_ptr()
+        assert not torch.isnan(out.float()).any() and torch.equal(out, first)
+    finally:
+        del graph
+        G.drop_stream_scratch(s.cuda_stream)
 
 
 def test_split_cus_falls_back_to_the_tail_plan():

@@ -180,6 +180,8 @@ def test_micro_decode_graph_replays_match_eager_gpu(stream):
                     micro_graph=False)
     eager.warm_shapes([1, 8, 64])
     a = _serve(eager, _requests(24, seed=9, gen=6))
+    counts = ("completed_total", "completed_tokens", "total_tokens", "matmul_flops", "micro_steps")
+    eager_counts = {c: getattr(eager, c) for c in counts}
     eager.close()
     graph = _engine("micro", device=dev, impl="hip", slots=16, budget=64, micro_stream=stream)
     graph.warm_shapes([1, 8, 64])
@@ -188,6 +190,8 @@ def test_micro_decode_graph_replays_match_eager_gpu(stream):
     assert graph.micro_graph_steps > 0
     assert sorted(a) == sorted(b) == list(range(24))
     assert {k: v[0] for k, v in a.items()} == {k: v[0] for k, v in b.items()}
+    # _serve blocks on every step: both engines take the same steps, so their bookkeeping agrees
+    assert {c: getattr(graph, c) for c in counts} == eager_counts
     assert graph.scratch_slot not in graph.free_micro and len(graph.free_micro) == graph.micro_slots
     graph.close()
 

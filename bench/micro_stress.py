@@ -11,6 +11,7 @@ admission -> last token p50/p99); a forward incomplete after
 ``--step-timeout`` seconds ends the run with BackendHung (exit 3).
 
     python bench/micro_stress.py --stream high --blas lt --seconds 40
+    python bench/micro_stress.py --stream partition --micro-cus 64 --micro-weights fp8   # the W8A16 micro-forwards
 """
 from __future__ import annotations
 
@@ -28,6 +29,8 @@ def main() -> int:
     ap.add_argument("--stream", default="high", choices=["high", "same", "partition"])
     ap.add_argument("--micro-cus", type=int, default=64)
     ap.add_argument("--micro-gemm", default="hip", choices=["hip", "rocblas"])
+    ap.add_argument("--micro-weights", default="bf16", choices=["bf16", "fp8"],
+                    help="layer weights of the micro-forwards (fp8: the W8A16 copy, ops.gemm.skinny_fp8)")
     ap.add_argument("--budget", type=int, default=4096)
     ap.add_argument("--slots", type=int, default=1536)
     ap.add_argument("--blas", default="", choices=["", "lt", "rocblas"],
@@ -50,7 +53,8 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     eng = BackendEngine(LlamaConfig.llama3_8b(), slots=a.slots, max_ctx=512, token_budget=a.budget, device=dev,
                         impl="hip", realtime_mode=a.mode, micro_stream=a.stream, micro_cus=a.micro_cus, micro_gemm=a.micro_gemm,
-                        micro_inflight=a.micro_inflight, step_timeout_s=a.step_timeout, micro_graph=not a.no_graph)
+                        micro_inflight=a.micro_inflight, step_timeout_s=a.step_timeout, micro_graph=not a.no_graph,
+                        micro_weights=a.micro_weights)
     eng.warm_shapes()
     eng.time_steps = True
     rng = np.random.default_rng(0)
@@ -109,7 +113,8 @@ def main() -> int:
                                   "rt_done": len(lat), "rt_p50_ms": round(float(np.percentile(la, 50)), 1),
                                   "rt_p99_ms": round(float(np.percentile(la, 99)), 1),
                                   "tok_s": round(eng.total_tokens / (t_rep - t0), 0),
-                                  "graph_steps": eng.micro_graph_steps}), flush=True)
+                                  "graph_steps": eng.micro_graph_steps, "micro_weights": a.micro_weights,
+                                  "weight_gib": round(eng.weight_bytes / 2 ** 30, 2)}), flush=True)
         eng.finish(block=True)
         eng.close()
         if a.stream == "partition":

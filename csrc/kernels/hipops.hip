@@ -545,6 +545,72 @@ static void skinny_gemm(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int
   check_launch();
 }
 
+// The same with e4m3 weight codes wq [N][K] bytes and fp32 column scales cs [N]
+// (skinny_partial_fp8_kernel, skinny_finalize_cs_kernel).
+static void skinny_gemm_fp8(uintptr_t a, uintptr_t wq, uintptr_t cs, uintptr_t c, int M, int N, int K, int epi,
+                            uintptr_t rs, uintptr_t ws, int nsplit, uintptr_t stream) {
+  require(M >= 1 && M <= SK_MAX_M, "skinny_gemm_fp8: M must be in [1, SK_MAX_M]");
+  require(N % SK_NB == 0, "skinny_gemm_fp8: N must be a multiple of 128");
+  require(nsplit >= 1 && K % (SK_KS * nsplit) == 0, "skinny_gemm_fp8: K must be a multiple of 128 * S");
+  require(epi == SK_EPI_STORE || epi == SK_EPI_RESID || epi == SK_EPI_SWIGLU, "skinny_gemm_fp8: unknown epilogue");
+  require(epi != SK_EPI_SWIGLU || N % 256 == 0, "skinny_gemm_fp8: SwiGLU needs N % 256 == 0");
+  require(a % 16 == 0 && wq % 16 == 0 && cs % 16 == 0 && cs != 0 && c % 16 == 0 && ws % 16 == 0 && ws != 0,
+          "skinny_gemm_fp8: alignment");
+  require((int64_t)N * K < (int64_t)1 << 31, "skinny_gemm_fp8: weight too large");
+  const int nm = (M + 127) / 128;
+  const int mt = nm > 1 ? 8 : (M + 15) / 16;
+  const dim3 grid(N / SK_NB * nm, nsplit);
+  const int kc = K / nsplit;
+  auto* A_ = P<const uint16_t>(a);
+  auto* W_ = P<const uint8_t>(wq);
+  auto* ws_ = P<float>(ws);
+#define SKQ_LAUNCH(T) \
+  hipLaunchKernelGGL(skinny_partial_fp8_kernel<T>, grid, dim3(256), 0, S(stream), A_, W_, ws_, M, N, K, kc, nm)
+  switch (mt) {
+    case 1: SKQ_LAUNCH(1); break;
+    case 2: SKQ_LAUNCH(2); break;
+    case 3: SKQ_LAUNCH(3); break;
+    case 4: SKQ_LAUNCH(4); break;
+    case 5: SKQ_LAUNCH(5); break;
+    case 6: SKQ_LAUNCH(6); break;
+    case 7: SKQ_LAUNCH(7); break;
+    default: SKQ_LAUNCH(8); break;
+  }
+#undef SKQ_LAUNCH
+  check_launch();
+  const int nout = epi == SK_EPI_SWIGLU ? N / 2 : N;
+  const dim3 fgrid((M * (nout / 4) + 255) / 256);
+  const float* rs_ = rs ? P<const float>(rs) : nullptr;
+  const float* cs_ = P<const float>(cs);
+  auto* C_ = P<uint16_t>(c);
+  if (epi == SK_EPI_STORE)
+    hipLaunchKernelGGL(skinny_finalize_cs_kernel<SK_EPI_STORE>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, cs_, C_);
+  else if (epi == SK_EPI_RESID)
+    hipLaunchKernelGGL(skinny_finalize_cs_kernel<SK_EPI_RESID>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, cs_, C_);
+  else
+    hipLaunchKernelGGL(skinny_finalize_cs_kernel<SK_EPI_SWIGLU>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, cs_, C_);
+  check_launch();
+}
+
+// codes [N][K] e4m3 + scale [N] fp32 of the bf16 rows w [N][K] (ops/quant.py)
+static void quant_rows_e4m3(uintptr_t w, int N, int K, uintptr_t codes, uintptr_t scale, uintptr_t stream) {
+  require(N >= 0 && K > 0 && K % 8 == 0, "quant_rows_e4m3: K must be a positive multiple of 8");
+  require(w % 16 == 0 && codes % 8 == 0 && scale % 4 == 0, "quant_rows_e4m3: alignment");
+  if (N == 0) return;
+  hipLaunchKernelGGL(quant_rows_e4m3_kernel, dim3(N), dim3(256), 0, S(stream), P<const uint16_t>(w), K,
+                     P<uint8_t>(codes), P<float>(scale));
+  check_launch();
+}
+
+// out[i] = bf16 bits of code byte i of in (n bytes, padded to whole words): the GEMM's decode, for tests
+static void fp8_decode(uintptr_t in, int n, uintptr_t out, uintptr_t stream) {
+  require(n >= 0 && in % 4 == 0 && out % 2 == 0, "fp8_decode: bad arguments");
+  if (n == 0) return;
+  hipLaunchKernelGGL(fp8_decode_kernel, dim3((n + 255) / 256), dim3(256), 0, S(stream), P<const uint32_t>(in), n,
+                     P<uint16_t>(out));
+  check_launch();
+}
+
 // ---------------------------------------------------------------------- CU partitions
 // Which hardware unit a workgroup ran on: HW_ID (cu / sh / se ids, gfx9
 // layout) and XCC_ID, read from the wave's hardware registers by lane 0.
@@ -664,6 +730,10 @@ PYBIND11_MODULE(_hipops, m) {
   m.def("hw_probe", &hw_probe, py::arg("blocks"), py::arg("spin"), py::arg("stream"));
   m.def("skinny_gemm", &skinny_gemm, py::arg("a"), py::arg("w"), py::arg("c"), py::arg("M"), py::arg("N"),
         py::arg("K"), py::arg("epi"), py::arg("rs"), py::arg("ws"), py::arg("S"), py::arg("stream"));
+  m.def("skinny_gemm_fp8", &skinny_gemm_fp8, py::arg("a"), py::arg("wq"), py::arg("cs"), py::arg("c"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("rs"), py::arg("ws"), py::arg("S"), py::arg("stream"));
+  m.def("quant_rows_e4m3", &quant_rows_e4m3);
+  m.def("fp8_decode", &fp8_decode);
   m.def("stream_with_cu_mask", &stream_with_cu_mask);
   m.def("stream_destroy", &stream_destroy);
   m.def("kv_move", &kv_move, py::arg("table"), py::arg("layers"), py::arg("slots"), py::arg("slot"), py::arg("n"),

@@ -25,6 +25,10 @@
 // Split-K partials are written to ws[S][M][N] fp32 and summed in split
 // order by the finalize kernel (deterministic: no atomics), which applies
 // the row scale and the epilogue and writes bf16.
+//
+// The second half of the file is the same GEMM over FP8 (e4m3) weight codes
+// with one fp32 scale a weight row (W8A16), the quantiser that makes them and
+// the decode both use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -187,10 +191,15 @@ __device__ __forceinline__ uint16_t sk_f2bf(float f) {
 //   RESID:  C[row][c] += sum, one bf16 rounding       (C: [M][N])
 //   SWIGLU: C[row][f]  = silu(g) * u over the swiglu-permuted columns of W
 //           (gate f at 256 t + 64 wc + c, up 32 columns later; C: [M][N / 2])
-template <int EPI>
-__global__ void __launch_bounds__(256)
-skinny_finalize_kernel(const float* __restrict__ ws, int S, int M, int N, const float* __restrict__ rs,
-                       uint16_t* __restrict__ C) {
+//
+// COLS (the fp8-weight GEMM): the sum of column n is first multiplied by
+// cs[n], the fp32 dequantisation scale of weight row n -- under SWIGLU the
+// gate and the up column each by its own entry (cs is indexed like the
+// permuted weight's rows).  The bf16 kernel instantiates COLS = false only.
+template <int EPI, bool COLS>
+__device__ __forceinline__ void sk_finalize(const float* __restrict__ ws, int S, int M, int N,
+                                            const float* __restrict__ rs, const float* __restrict__ cs,
+                                            uint16_t* __restrict__ C) {
   const int Nout = EPI == SK_EPI_SWIGLU ? N / 2 : N;
   const int per_row = Nout / 4;
   const int gid = blockIdx.x * 256 + threadIdx.x;
@@ -206,6 +215,10 @@ skinny_finalize_kernel(const float* __restrict__ ws, int S, int M, int N, const 
       g += *reinterpret_cast<const sk_f32x4*>(p + gcol);
       u += *reinterpret_cast<const sk_f32x4*>(p + gcol + 32);
     }
+    if constexpr (COLS) {
+      g *= *reinterpret_cast<const sk_f32x4*>(cs + gcol);
+      u *= *reinterpret_cast<const sk_f32x4*>(cs + gcol + 32);
+    }
     uint16_t o[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -217,6 +230,7 @@ skinny_finalize_kernel(const float* __restrict__ ws, int S, int M, int N, const 
   } else {
     sk_f32x4 v = sk_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < S; ++s) v += *reinterpret_cast<const sk_f32x4*>(ws + ((size_t)s * M + row) * N + c4);
+    if constexpr (COLS) v *= *reinterpret_cast<const sk_f32x4*>(cs + c4);
     uint2* cp = reinterpret_cast<uint2*>(C + (size_t)row * N + c4);
     float r[4] = {v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale};
     if constexpr (EPI == SK_EPI_RESID) {
@@ -228,6 +242,247 @@ skinny_finalize_kernel(const float* __restrict__ ws, int S, int M, int N, const 
     }
     *cp = make_uint2((uint32_t)sk_f2bf(r[0]) | ((uint32_t)sk_f2bf(r[1]) << 16),
                      (uint32_t)sk_f2bf(r[2]) | ((uint32_t)sk_f2bf(r[3]) << 16));
+  }
+}
+
+template <int EPI>
+__global__ void __launch_bounds__(256)
+skinny_finalize_kernel(const float* __restrict__ ws, int S, int M, int N, const float* __restrict__ rs,
+                       uint16_t* __restrict__ C) {
+  sk_finalize<EPI, false>(ws, S, M, N, rs, nullptr, C);
+}
+
+template <int EPI>
+__global__ void __launch_bounds__(256)
+skinny_finalize_cs_kernel(const float* __restrict__ ws, int S, int M, int N, const float* __restrict__ rs,
+                          const float* __restrict__ cs, uint16_t* __restrict__ C) {
+  sk_finalize<EPI, true>(ws, S, M, N, rs, cs, C);
+}
+
+// ---------------------------------------------------------------------- fp8 (e4m3) weights, W8A16
+// The weights as OCP e4m3fn codes (one byte an element, [N][K]) with one fp32
+// scale a row (ops/quant.py holds the contract); A stays bf16.  The codes are
+// decoded to bf16 in registers right before the bf16 MFMA (every finite code
+// is exactly a bf16 number), so the arithmetic is skinny_partial_kernel's on
+// the decoded weights and the row's scale waits for the finalize kernel.
+
+typedef __attribute__((ext_vector_type(2))) __bf16 sk_bf16x2;
+
+// bytes 2 HI, 2 HI + 1 of w -> two bf16 (low half first): the scaled pack
+// conversion with scale 1, one VALU op a pair.  (v_cvt_pk_f32_fp8 + packing
+// the two high halves measured 0-7 % slower per GEMM: profiles/skinny_fp8.md.)
+template <bool HI>
+__device__ __forceinline__ uint32_t sk_fp8x2_bf16(uint32_t w) {
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+}
+
+__device__ __forceinline__ sk_bf16x8 sk_fp8x8_bf16(uint32_t lo, uint32_t hi) {
+  const sk_u32x4 r = {sk_fp8x2_bf16<false>(lo), sk_fp8x2_bf16<true>(lo), sk_fp8x2_bf16<false>(hi),
+                      sk_fp8x2_bf16<true>(hi)};
+  return __builtin_bit_cast(sk_bf16x8, r);
+}
+
+// out[i] = bf16 bits of the code in byte i % 4 of in[i / 4]: the GEMM's decode, for tests
+__global__ void __launch_bounds__(256) fp8_decode_kernel(const uint32_t* __restrict__ in, int n,
+                                                         uint16_t* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t w = in[i >> 2];
+  const uint32_t p = (i & 2) ? sk_fp8x2_bf16<true>(w) : sk_fp8x2_bf16<false>(w);
+  out[i] = (uint16_t)((i & 1) ? p >> 16 : p);
+}
+
+constexpr int SKQ_ST = 5;           // register stages of the fp8 weight ring
+
+// skinny_partial_kernel with Wq = e4m3 codes [N][K].  Same blocks, chunks of
+// M, 128-deep steps and K permutation: MFMA step s4 of lane (fr, fq) takes K
+// chunk (fq * 4 + s4) * 8, which for byte weights makes a lane's read of a
+// step one contiguous 32-byte run (a weight row's 128 bytes = one cache line
+// per four lanes).  The runs are half the bf16 kernel's, so the ring is
+// SKQ_ST = 5 stages deep -- four steps of loads behind the one computed, the
+// same 256 bytes a lane a fragment in flight -- in 80 registers (bf16: 96).
+template <int MT>
+__global__ void __launch_bounds__(256)
+skinny_partial_fp8_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq, float* __restrict__ ws,
+                          int M, int N, int K, int kc, int nm) {
+  __shared__ __align__(16) uint16_t As[2][MT * 16][SK_LDA];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int ncb = N / SK_NB;
+  int cb = blockIdx.x, mc = 0;
+  if (nm > 1) {
+    if ((ncb & 7) == 0) {
+      const int b = blockIdx.x, idx = b >> 3;
+      cb = (idx / nm) * 8 + (b & 7);
+      mc = idx % nm;
+    } else {
+      cb = blockIdx.x / nm;
+      mc = blockIdx.x % nm;
+    }
+  }
+  const int m0 = mc * (MT * 16);
+  const int Ml = min(M - m0, MT * 16);
+  const int n0 = cb * SK_NB + w * 32;
+  const int kb = blockIdx.y * kc;
+  const int nsteps = kc / SK_KS;
+  // weight rows of this lane's two fragments; byte offset of its 32-byte run
+  const uint8_t* wp0 = Wq + (size_t)(n0 + fr) * K + kb + fq * 32;
+  const uint8_t* wp1 = wp0 + (size_t)16 * K;
+  constexpr int RG = (MT * 16 + 63) / 64;
+  const int arow = tid >> 2, acb = (tid & 3) * 4;
+  bool a_on[RG], a_live[RG];
+  const uint16_t* ap[RG];
+#pragma unroll
+  for (int g = 0; g < RG; ++g) {
+    const int r = g * 64 + arow;
+    a_on[g] = r < MT * 16;
+    a_live[g] = a_on[g] && r < Ml;
+    ap[g] = A + (size_t)(m0 + (a_live[g] ? r : 0)) * K + kb + acb * 8;
+  }
+
+  sk_f32x4 acc[MT][2];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    acc[m][0] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[m][1] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // stage k % SKQ_ST holds step k: [fragment][16-byte half of the run]
+  sk_u32x4 wb[SKQ_ST][2][2];
+  sk_u32x4 ab[RG][4];
+  auto load_w = [&](auto stc, int step) {
+    constexpr int ST = decltype(stc)::value;
+    const int ko = step * SK_KS;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      wb[ST][0][i] = *reinterpret_cast<const sk_u32x4*>(wp0 + ko + 16 * i);
+      wb[ST][1][i] = *reinterpret_cast<const sk_u32x4*>(wp1 + ko + 16 * i);
+    }
+  };
+  auto load_a = [&](int step) {
+    const int ko = step * SK_KS;
+#pragma unroll
+    for (int g = 0; g < RG; ++g)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        ab[g][i] = a_live[g] ? *reinterpret_cast<const sk_u32x4*>(ap[g] + ko + 8 * i) : sk_u32x4{0u, 0u, 0u, 0u};
+  };
+  auto store_a = [&](int buf) {
+#pragma unroll
+    for (int g = 0; g < RG; ++g) {
+      if (a_on[g]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          *reinterpret_cast<sk_u32x4*>(&As[buf][g * 64 + arow][(acb + i) * 8]) = ab[g][i];
+      }
+    }
+  };
+  // one step from register stage CUR (= step % SKQ_ST) and A buffer step % 2;
+  // the codes of step + SKQ_ST - 1 and the A tile of step + 1 load meanwhile
+  auto run_step = [&](auto curc, int step) {
+    constexpr int CUR = decltype(curc)::value;
+    if (step + SKQ_ST - 1 < nsteps)
+      load_w(std::integral_constant<int, (CUR + SKQ_ST - 1) % SKQ_ST>{}, step + SKQ_ST - 1);
+    const bool more = step + 1 < nsteps;
+    if (more) load_a(step + 1);
+    const int abuf = step & 1;
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      // K chunk s4 of the run: bytes 8 s4 .. 8 s4 + 7
+      const sk_bf16x8 b0 = sk_fp8x8_bf16(wb[CUR][0][s4 >> 1][(s4 & 1) * 2], wb[CUR][0][s4 >> 1][(s4 & 1) * 2 + 1]);
+      const sk_bf16x8 b1 = sk_fp8x8_bf16(wb[CUR][1][s4 >> 1][(s4 & 1) * 2], wb[CUR][1][s4 >> 1][(s4 & 1) * 2 + 1]);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const sk_bf16x8 a = *reinterpret_cast<const sk_bf16x8*>(&As[abuf][m * 16 + fr][(fq * 4 + s4) * 8]);
+        acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b0, acc[m][0], 0, 0, 0);
+        acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b1, acc[m][1], 0, 0, 0);
+      }
+    }
+    if (more) store_a(abuf ^ 1);
+    __syncthreads();
+  };
+
+  load_a(0);
+  load_w(std::integral_constant<int, 0>{}, 0);
+  if (nsteps > 1) load_w(std::integral_constant<int, 1>{}, 1);
+  if (nsteps > 2) load_w(std::integral_constant<int, 2>{}, 2);
+  if (nsteps > 3) load_w(std::integral_constant<int, 3>{}, 3);
+  store_a(0);
+  __syncthreads();
+  for (int step = 0; step < nsteps; step += SKQ_ST) {
+    run_step(std::integral_constant<int, 0>{}, step);
+    if (step + 1 < nsteps) run_step(std::integral_constant<int, 1>{}, step + 1);
+    if (step + 2 < nsteps) run_step(std::integral_constant<int, 2>{}, step + 2);
+    if (step + 3 < nsteps) run_step(std::integral_constant<int, 3>{}, step + 3);
+    if (step + 4 < nsteps) run_step(std::integral_constant<int, 4>{}, step + 4);
+  }
+  float* out = ws + (size_t)blockIdx.y * M * N;
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = m * 16 + fq * 4 + e;
+        if (row < Ml) out[(size_t)(m0 + row) * N + n0 + j * 16 + fr] = acc[m][j][e];
+      }
+}
+
+// Rows of bf16 weights -> e4m3 codes + one power-of-two scale a row, bit for
+// bit ops/quant.py's quantize_rows_e4m3: one block a row; absmax over the
+// bf16 magnitudes (as integers), scale 2^e = the smallest power of two with
+// absmax / 2^e <= 448 (e >= -126; an all-zero row: scale 1, codes 0), then
+// round-to-nearest-even of w / 2^e to e4m3 -- the normal range by rounding
+// the fp32 mantissa to 3 bits, below 2^-6 by the fp32 add of 2^14 (whose ulp
+// is the subnormal step 2^-9).  |w / 2^e| <= 448 by construction: no NaN code.
+__device__ __forceinline__ uint32_t sk_e4m3_rne(float x) {
+  const uint32_t b = __float_as_uint(x), sign = (b >> 24) & 0x80u;
+  uint32_t u = b & 0x7fffffffu;
+  if (u >= 0x3c800000u) {                            // >= 2^-6: normal in e4m3
+    u += 0x7ffffu + ((u >> 20) & 1u);
+    return sign | ((u >> 20) - (120u << 3));
+  }
+  const float f = __uint_as_float(u) + 16384.f;      // 2^14: the add rounds to multiples of 2^-9
+  return sign | (__float_as_uint(f) - 0x46800000u);
+}
+
+__global__ void __launch_bounds__(256)
+quant_rows_e4m3_kernel(const uint16_t* __restrict__ W, int K, uint8_t* __restrict__ codes, float* __restrict__ scale) {
+  __shared__ uint32_t red[4];
+  const uint16_t* wr = W + (size_t)blockIdx.x * K;
+  uint8_t* cr = codes + (size_t)blockIdx.x * K;
+  const int nv = K / 8;
+  uint32_t amax = 0;
+  for (int v = threadIdx.x; v < nv; v += 256) {
+    const sk_u32x4 x = *reinterpret_cast<const sk_u32x4*>(wr + v * 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) amax = max(amax, max(x[i] & 0x7fffu, (x[i] >> 16) & 0x7fffu));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = max(amax, (uint32_t)__shfl_xor((int)amax, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
+  __syncthreads();
+  amax = max(max(red[0], red[1]), max(red[2], red[3]));
+  if (amax == 0) {                                   // (uniform over the block)
+    for (int v = threadIdx.x; v < nv; v += 256) *reinterpret_cast<uint2*>(cr + v * 8) = make_uint2(0u, 0u);
+    if (threadIdx.x == 0) scale[blockIdx.x] = 1.f;
+    return;
+  }
+  // absmax = 1.m * 2^(E - 127): <= 1.75 * 2^(e + 8) <=> e = E - 135 (+ 1 when 1.m > 1.75)
+  const int E = (int)(amax >> 7);
+  int e = E - 135 + ((amax & 0x7fu) > 0x60u ? 1 : 0);
+  if (E == 0 || e < -126) e = -126;
+  const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
+  if (threadIdx.x == 0) scale[blockIdx.x] = __uint_as_float((uint32_t)(127 + e) << 23);
+  for (int v = threadIdx.x; v < nv; v += 256) {
+    const sk_u32x4 x = *reinterpret_cast<const sk_u32x4*>(wr + v * 8);
+    uint32_t o[2] = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t c0 = sk_e4m3_rne(__uint_as_float(x[i] << 16) * inv);
+      const uint32_t c1 = sk_e4m3_rne(__uint_as_float(x[i] & 0xffff0000u) * inv);
+      o[i >> 1] |= (c0 | (c1 << 8)) << ((i & 1) * 16);
+    }
+    *reinterpret_cast<uint2*>(cr + v * 8) = make_uint2(o[0], o[1]);
   }
 }
 

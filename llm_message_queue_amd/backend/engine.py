@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from ..models.llama_stub import LlamaConfig, LlamaStub
-from ..ops.gemm import row_scale_len
+from ..ops.gemm import SKINNY_CHUNKED_MAX_M, row_scale_len
 from ..ops.sampling import inv_temperature, row_keys
 
 
@@ -156,7 +156,7 @@ class BackendEngine:
                  realtime_step_tokens: int = 0, fused_rms=None, realtime_mode: str = "",
                  micro_slots: int = 96, micro_budget: int = 512, micro_inflight: int = 1,
                  micro_stream: str = "partition", micro_cus: int = 64, micro_gemm: str = "hip",
-                 library_gemm: bool = False, micro_graph: bool = True):
+                 library_gemm: bool = False, micro_graph: bool = True, micro_weights: str = "bf16"):
         self.cfg = model_cfg
         # a queued forward older than this raises BackendHung (0 = wait forever)
         self.step_timeout_s = float(step_timeout_s)
@@ -236,6 +236,21 @@ class BackendEngine:
         if micro_gemm not in ("hip", "rocblas"):
             raise ValueError(f"micro_gemm must be hip / rocblas, not {micro_gemm!r}")
         self.micro_gemm = micro_gemm
+        # the layer weights the micro-forwards read: "bf16" = the serving
+        # pool's, "fp8" = an e4m3 copy with one scale a row (W8A16: half the
+        # bytes a micro-forward streams; ops.quant, ops.gemm.skinny_fp8).  A
+        # request of the micro pool then sees the quantised model in all its
+        # forwards, eager or graph-replayed, so its tokens differ from the
+        # serving pool's (``Request.micro`` tells which pool served it).
+        # Without micro-forwards the mode only costs the copy's memory.
+        if micro_weights not in ("bf16", "fp8"):
+            raise ValueError(f"micro_weights must be bf16 / fp8, not {micro_weights!r}")
+        if micro_weights == "fp8" and micro_gemm == "rocblas":
+            raise ValueError("micro_weights fp8 needs micro_gemm hip (the library has no W8A16 kernel)")
+        if micro_weights == "fp8" and self.micro and self.micro_budget > SKINNY_CHUNKED_MAX_M:
+            raise ValueError(f"micro_weights fp8: micro_budget {self.micro_budget} exceeds the fp8 kernel's "
+                             f"{SKINNY_CHUNKED_MAX_M} rows")
+        self.micro_weights = micro_weights
         if self.micro_cus and micro_gemm == "rocblas":
             import os
             # rocBLAS may hand some GEMMs to hipBLASLt on gfx950: keep them classic
@@ -244,7 +259,7 @@ class BackendEngine:
                                residual_in_gemm=residual_in_gemm, split_qkv=split_qkv, fused_mlp=fused_mlp,
                                fused_qkv=fused_qkv, row_scale_norm=row_scale_norm, fused_head=fused_head,
                                fused_resid=fused_resid, fused_rms=fused_rms, prune_last=prune_last,
-                               library_gemm=library_gemm)
+                               library_gemm=library_gemm, small_weights=micro_weights)
         self.impl = impl
         self.weight_bytes = self.model.weight_bytes()
         self.active: Dict[int, Request] = {}            # slot -> request
@@ -847,7 +862,10 @@ class BackendEngine:
         rocBLAS.  ``rocblas`` applies to eager micro-forwards only: the
         captured graphs (``graph``: the capture and its two warm-ups) always
         hold the hand-written kernels, so graph-replayed decode steps run
-        those whatever ``micro_gemm`` says."""
+        those whatever ``micro_gemm`` says.  ``micro_weights = "fp8"``: every
+        micro-forward, eager or captured, reads the quantised layer weights."""
+        if self.micro_weights == "fp8":
+            skw["quant"] = True
         if self.micro_cus and self.micro_gemm == "rocblas" and not graph:
             with _blas("cublas"):
                 return self.model.forward(tok, pos, slot, samp, tiles=tiles, n_dec=n_dec, **skw)

@@ -49,7 +49,8 @@ def _build_engine(cfg, model: str, device, job: str = ""):
     page = SlotPage(f"serve{job or os.getpid()}", rank)
     mcfg = LlamaConfig.by_name(model)
     slots = fit_slots(mcfg, cfg.gpu.slots_per_gpu, cfg.backend.max_ctx, cfg.gpu.hbm_reserve_gb,
-                      torch.cuda.get_device_properties(device).total_memory)
+                      torch.cuda.get_device_properties(device).total_memory,
+                      extra_weight_bytes=mcfg.quant_bytes() if cfg.backend.micro_weights == "fp8" else 0)
     return BackendEngine(mcfg, slots=slots, max_ctx=cfg.backend.max_ctx,
                          token_budget=cfg.backend.token_budget, device=device, impl="hip", page=page, gpu_index=rank,
                          step_timeout_s=cfg.backend.step_timeout / 1e9,
@@ -57,15 +58,18 @@ def _build_engine(cfg, model: str, device, job: str = ""):
                          realtime_mode=cfg.backend.realtime_mode, micro_slots=cfg.backend.micro_slots,
                          micro_inflight=cfg.backend.micro_inflight, micro_stream=cfg.backend.micro_stream,
                          micro_cus=cfg.backend.micro_cus, micro_gemm=cfg.backend.micro_gemm,
-                         library_gemm=cfg.backend.library_gemm, micro_graph=cfg.backend.micro_graph), page
+                         library_gemm=cfg.backend.library_gemm, micro_graph=cfg.backend.micro_graph,
+                         micro_weights=cfg.backend.micro_weights), page
 
 
-def fit_slots(mcfg, slots: int, max_ctx: int, reserve_gb: float, total_bytes: int) -> int:
+def fit_slots(mcfg, slots: int, max_ctx: int, reserve_gb: float, total_bytes: int,
+              extra_weight_bytes: int = 0) -> int:
     """``gpu.hbm_reserve_gb``: batch slots whose KV cache (slots x max_ctx x
-    K/V bytes per token) fits next to the bf16 weights with that much HBM
-    left free; fewer than configured -> capped, with a warning."""
+    K/V bytes per token) fits next to the bf16 weights (and
+    ``extra_weight_bytes``: the FP8 copy of ``backend.micro_weights``) with
+    that much HBM left free; fewer than configured -> capped, with a warning."""
     per_slot = max_ctx * mcfg.layers * 2 * mcfg.kv_heads * mcfg.head_dim * 2
-    room = total_bytes - int(reserve_gb * (1 << 30)) - mcfg.param_count() * 2
+    room = total_bytes - int(reserve_gb * (1 << 30)) - mcfg.param_count() * 2 - int(extra_weight_bytes)
     fit = max(0, room // per_slot) if per_slot > 0 else slots
     if fit < slots:
         from ..utils.logging import get_logger

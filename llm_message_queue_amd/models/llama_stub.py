@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from ..ops import gemm as G
+from ..ops import quant as Qn
 from ..ops.llama_ops import get_ops, rope_tables
 
 
@@ -65,6 +66,18 @@ class LlamaConfig:
         per = qkv + d * d + 2 * d * f + d * f + 2 * d
         return self.layers * per + 2 * self.vocab * d + d
 
+    def quant_bytes(self) -> int:
+        """Bytes of the layers' FP8 copy (``small_weights="fp8"``): a byte
+        an element of the four layer matrices + a float32 scale a row."""
+        d, f = self.dim, self.ffn
+        nqkv = (self.heads + 2 * self.kv_heads) * self.head_dim
+        return self.layers * (nqkv * d + d * d + 3 * d * f + 4 * (nqkv + d + 2 * f + d))
+
+
+# the layer weights a ``quant`` forward reads as FP8 (e4m3 codes + a scale a row)
+QUANT_NAMES = ("wqkv", "wo", "w_gu", "w_down")
+QUANT_NAMES_BY_MODE = {"bf16": (), "fp8": QUANT_NAMES}
+
 
 class LlamaStub:
     def __init__(self, cfg: LlamaConfig, slots: int, max_ctx: int, device="cuda", impl: str = "hip",
@@ -73,9 +86,11 @@ class LlamaStub:
                  fused_qkv: Optional[bool] = None, min_fused_qkv_tokens: int = 2048, row_scale_norm: bool = True,
                  fused_head: Optional[bool] = None, fused_resid: Optional[bool] = None,
                  fused_rms: Optional[bool] = None,
-                 prune_last: bool = True, library_gemm: bool = False):
+                 prune_last: bool = True, library_gemm: bool = False, small_weights: str = "bf16"):
         if cfg.head_dim != 128:
             raise ValueError("kernels assume head_dim = 128")
+        if small_weights not in QUANT_NAMES_BY_MODE:
+            raise ValueError(f"small_weights must be bf16 / fp8, not {small_weights!r}")
         self.cfg = cfg
         self.device = torch.device(device)
         self.ops = get_ops(impl)
@@ -140,6 +155,16 @@ class LlamaStub:
         # fused paths take the raw residual rows + a per-row RMSNorm scale
         # (True) or an rmsnorm'd copy of the rows (False, A/B)
         self.row_scale_norm = bool(row_scale_norm)
+        # "fp8": every layer also holds its four weight matrices as e4m3
+        # codes + one power-of-two scale a row (ops.quant), which a forward
+        # with ``quant`` reads instead of the bf16 ones (W8A16: half the
+        # bytes a small step streams; ops.gemm.skinny_fp8).  The embedding
+        # and the LM head stay bf16.
+        self.small_weights = small_weights
+        if small_weights == "fp8" and impl == "hip" and not (
+                self.fused_mlp and self.fused_qkv and self.row_scale_norm and self.residual_in_gemm):
+            raise ValueError("small_weights fp8 needs the fused paths (fused_mlp, fused_qkv, row_scale_norm, "
+                             "residual_in_gemm)")
         g = torch.Generator(device=self.device).manual_seed(seed)
         std = 0.02
 
@@ -168,6 +193,8 @@ class LlamaStub:
             if self.fused_mlp:
                 L["w_gu"], L["mlp_norm"] = self._fold_norm(L["w_gu"], L["mlp_norm"])
             L["w_gu"] = self._gu_layout(L["w_gu"])
+            if small_weights == "fp8":
+                L["fp8"] = {k: self._quantize(L[k]) for k in QUANT_NAMES}
             self.layers.append(L)
         # KV cache: per layer [slots, kv_heads, max_ctx, head_dim]
         self.kcache = [torch.zeros((slots, hkv, max_ctx, hd), dtype=dtype, device=self.device)
@@ -188,11 +215,33 @@ class LlamaStub:
             return w_gu
         return G.swiglu_permute(w_gu)
 
+    def _quantize(self, w: torch.Tensor):
+        """(codes, scale) of one layer weight, on the device kernel with the
+        HIP ops (bit-equal to the host twin)."""
+        if self.impl == "hip" and w.is_cuda:
+            return G.quantize_rows(w)
+        codes, scale = Qn.quantize_rows_e4m3(w)
+        return codes.to(w.device), scale.to(w.device)
+
+    def _dequantized(self, i: int) -> dict:
+        """Layer ``i`` with its quantised weights decoded back to bf16: what
+        the reference ops compute a ``quant`` forward with (a cache of the
+        reference path only; the HIP path reads the codes)."""
+        cache = self.__dict__.setdefault("_deq_layers", {})
+        if i not in cache:
+            L = dict(self.layers[i])
+            for k, (codes, scale) in L.pop("fp8").items():
+                L[k] = Qn.dequantize(codes, scale)
+            cache[i] = L
+        return cache[i]
+
     def weight_bytes(self) -> int:
         n = self.embed.numel() + self.lm_head.numel() + self.final_norm.numel()
+        q = 0
         for L in self.layers:
-            n += sum(t.numel() for t in L.values())
-        return n * 2
+            n += sum(t.numel() for t in L.values() if torch.is_tensor(t))
+            q += sum(c.numel() + 4 * s.numel() for c, s in L.get("fp8", {}).values())
+        return n * 2 + q
 
     def kv_bytes(self) -> int:
         return sum(t.numel() * 2 for t in self.kcache) * 2
@@ -201,7 +250,7 @@ class LlamaStub:
     def forward(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 sample_idx: torch.Tensor, tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
                 small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
-                keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+                keys: Optional[torch.Tensor] = None, quant: bool = False) -> torch.Tensor:
         """One step over T tokens; returns greedy next-token ids for the rows
         in ``sample_idx`` (the last token of each request's chunk).  With
         ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
@@ -214,12 +263,15 @@ class LlamaStub:
         (a realtime micro-forward on its CU partition) -- every GEMM on the
         hand-written kernels whatever the row count (no library kernel, none
         of whose persistent / stream-K grids assume the whole chip), split-K
-        where the tiles cannot fill the partition."""
+        where the tiles cannot fill the partition.  ``quant`` (a model built
+        with ``small_weights="fp8"``): every layer GEMM of this forward reads
+        the FP8 weights (``hidden``); the head stays bf16."""
         if self.prune_last and self.residual_in_gemm:
-            sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus)
+            sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus,
+                              quant=quant)
         else:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec,
-                              small_cus=small_cus).index_select(0, sample_idx)
+                              small_cus=small_cus, quant=quant).index_select(0, sample_idx)
         hand = small_cus or not self.library_gemm
         if inv_temp is not None and keys is not None:
             return self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
@@ -229,7 +281,7 @@ class LlamaStub:
     @torch.no_grad()
     def hidden(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
-               rows: Optional[torch.Tensor] = None, small_cus: int = 0) -> torch.Tensor:
+               rows: Optional[torch.Tensor] = None, small_cus: int = 0, quant: bool = False) -> torch.Tensor:
         """The 32-layer trunk: final-normed hidden states [T, d] (writes the
         step's K/V into the cache).
 
@@ -244,12 +296,25 @@ class LlamaStub:
         these rows for its o projection and MLP -- the other rows' outputs of
         that layer feed nothing (no later layer reads them, and the LM head
         reads only the sampled rows), so the result for ``rows`` is the same
-        computation.  Returns [len(rows), d] then, else [T, d]."""
+        computation.  Returns [len(rows), d] then, else [T, d].
+
+        ``quant``: the four GEMMs of every layer read the layer's FP8 weights
+        -- with the HIP ops on ``ops.gemm.skinny_fp8`` at any row count up to
+        ``SKINNY_CHUNKED_MAX_M`` (never a bf16 kernel: a request sees one
+        model in all its forwards), with the reference ops on the decoded
+        weights (``ops.quant.dequantize``), which is the same arithmetic."""
         cfg, ops = self.cfg, self.ops
+        if quant and self.small_weights != "fp8":
+            raise ValueError("quant forward on a model built without small_weights='fp8'")
+        layers = self.layers
+        if quant and self.impl != "hip":
+            layers, quant = [self._dequantized(i) for i in range(len(self.layers))], False
         if not self.residual_in_gemm:
-            return self._hidden_residual_norm(tokens, pos, slot, tiles, n_dec)
+            return self._hidden_residual_norm(tokens, pos, slot, tiles, n_dec, layers)
         res = F.embedding(tokens, self.embed)            # [T, d], updated in place
         T = res.shape[0]
+        if quant and T > G.SKINNY_CHUNKED_MAX_M:
+            raise ValueError(f"quant forward of {T} rows: the fp8 kernel takes at most {G.SKINNY_CHUNKED_MAX_M}")
         small = small_cus > 0 and self.impl == "hip"
         nolib = not self.library_gemm and self._cus > 0
         # the skinny kernel (a stream over the weights) for qkv up to
@@ -268,13 +333,19 @@ class LlamaStub:
             # every tile split when twice the tiles fit one wave; else the
             # default half-empty-last-wave plan (split_plan)
             qkv_split = {"split": True, "split_full": f} if f is not None else {}
-        last = len(self.layers) - 1
+        last = len(layers) - 1
         if rows is not None and rows.numel() == T:
             rows = None                                  # every row sampled: nothing to drop
 
         scale = None                                     # row scales of res from the previous down GEMM
-        for i, L in enumerate(self.layers):
-            if skinny:
+        for i, L in enumerate(layers):
+            if quant:
+                qkv = torch.empty((T, L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
+                G.skinny_fp8(res, *L["fp8"]["wqkv"], qkv, G.SK_STORE, row_scale=ops.row_rms(res, cfg.eps),
+                             cus=sk_cus or 32)
+                q = ops.rope_kv(qkv, pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i],
+                                self.vcache[i])
+            elif skinny:
                 qkv = torch.empty((T, L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
                 G.skinny(res, L["wqkv"], qkv, G.SK_STORE, row_scale=ops.row_rms(res, cfg.eps), cus=sk_cus)
                 q = ops.rope_kv(qkv, pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i],
@@ -294,7 +365,7 @@ class LlamaStub:
                     return res[:0]                       # chunks): K/V written, no row kernel gets 0 rows
                 res, a = res.index_select(0, rows), a.index_select(0, rows)
             scale = self._mlp_block(res, a, L, want_scale=rows_qkv and self.row_scale_norm and i < last,
-                                    small_cus=small_cus if small else 0)
+                                    small_cus=small_cus if small else 0, quant=quant)
         return ops.rmsnorm(res, self.final_norm, cfg.eps)
 
     @torch.no_grad()
@@ -316,16 +387,25 @@ class LlamaStub:
         return n
 
     def _mlp_block(self, res: torch.Tensor, a: torch.Tensor, L: dict, want_scale: bool = False,
-                   small_cus: int = 0):
+                   small_cus: int = 0, quant: bool = False):
         """res += o(a); res += down(swiglu(norm(res))) -- in place, with the
         fused-path choices made for this block's row count.  Returns the
         RMSNorm row scales of the final ``res`` when ``want_scale`` and the
         down GEMM produced them in its epilogue (``fused_rms``), else None.
         ``small_cus``: a micro-forward's small step on its CU partition --
-        the hand-written kernels at any row count, split-K (``forward``)."""
+        the hand-written kernels at any row count, split-K (``forward``).
+        ``quant``: o, gate/up and down on the FP8 weights in ``L["fp8"]``
+        (``skinny_fp8``, any row count it takes)."""
         cfg, ops = self.cfg, self.ops
         M = res.shape[0]
         small = small_cus > 0
+        if quant:
+            cus = small_cus or self._cus or 32
+            G.skinny_fp8(a, *L["fp8"]["wo"], res, G.SK_RESID, cus=cus)
+            act = torch.empty((M, L["w_gu"].shape[0] // 2), dtype=res.dtype, device=res.device)
+            G.skinny_fp8(res, *L["fp8"]["w_gu"], act, G.SK_SWIGLU, row_scale=ops.row_rms(res, cfg.eps), cus=cus)
+            G.skinny_fp8(act, *L["fp8"]["w_down"], res, G.SK_RESID, cus=cus)
+            return None
         # library-free (``library_gemm`` False): the hand-written kernels at
         # every row count, split-K where whole tiles leave CUs idle
         nolib = not small and not self.library_gemm and self._cus > 0
@@ -390,15 +470,16 @@ class LlamaStub:
                                        self.scale, n_dec=n_dec)
         return ops.attention(q, self.kcache[i], self.vcache[i], pos, slot, cfg.heads, cfg.kv_heads, self.scale)
 
-    def _hidden_residual_norm(self, tokens, pos, slot, tiles, n_dec):
+    def _hidden_residual_norm(self, tokens, pos, slot, tiles, n_dec, layers=None):
         """residual_in_gemm=False (A/B only): F.linear o / down projections and
         residual-add RMSNorm kernels instead of beta = 1 GEMM epilogues."""
         cfg, ops = self.cfg, self.ops
+        layers = self.layers if layers is None else layers
         h = F.embedding(tokens, self.embed)
         res = h.clone()
-        x = ops.rmsnorm(h, self.layers[0]["attn_norm"], cfg.eps)
+        x = ops.rmsnorm(h, layers[0]["attn_norm"], cfg.eps)
         out = None
-        for i, L in enumerate(self.layers):
+        for i, L in enumerate(layers):
             if i > 0:
                 x = ops.rmsnorm(out, L["attn_norm"], cfg.eps, residual=res)
             a = self._attend(self._qkv(x, L, i, pos, slot), i, pos, slot, tiles, n_dec)

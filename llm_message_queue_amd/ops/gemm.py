@@ -11,7 +11,8 @@ RMSNorm's row scales) and ``lm_head_argmax`` / ``lm_head_sample`` (the LM head
 with greedy or per-row temperature sampling, no logits tensor).  The first
 three take ``row_scale`` (the folded RMSNorm).  A step too small to fill the
 CUs runs split-K (:func:`split_plan`, :func:`split_all`) or, below
-``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`).
+``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`; :func:`skinny_fp8`
+over FP8 weight codes, :func:`quantize_rows` to make them -- ``ops.quant``).
 
 CPU / reference path: :func:`swiglu_reference` (fp32 math of the same op).
 """
@@ -413,6 +414,73 @@ def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_sc
         rs = row_scale.data_ptr()
     _native.require_hipops().skinny_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, epi, rs,
                                          ws.data_ptr(), S, stream)
+    return out
+
+
+def skinny_fp8(x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, out: torch.Tensor, epi: int,
+               row_scale=None, cus: int = 32, splits: int = 0):
+    """:func:`skinny` over FP8 weights (W8A16): ``codes`` uint8 [N][K] e4m3fn
+    and ``col_scale`` float32 [N], one scale a weight row (``ops.quant``), so
+    ``out (+)= (x . codesᵀ) * col_scale[n] * row_scale[m]`` -- the codes are
+    decoded to bf16 in registers, the scales applied in fp32 by the finalize
+    kernel.  Under SK_SWIGLU ``codes`` / ``col_scale`` follow the
+    swiglu-permuted row order.  Same shapes, split-K rule, scratch and
+    determinism as :func:`skinny`."""
+    _check(x, "x")
+    _check(out, "out")
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous() or codes.data_ptr() % 16:
+        raise ValueError("skinny_fp8: codes must be contiguous 16-byte-aligned uint8 [N][K]")
+    M, K = x.shape
+    N = codes.shape[0]
+    if col_scale.dtype != torch.float32 or tuple(col_scale.shape) != (N,) or not col_scale.is_contiguous() \
+            or col_scale.data_ptr() % 16:
+        raise ValueError("skinny_fp8: col_scale must be contiguous 16-byte-aligned float32 [N]")
+    if codes.device != x.device or col_scale.device != x.device:
+        raise ValueError("skinny_fp8: codes / col_scale must be on x's device")
+    if codes.shape[1] != K or not 1 <= M <= SKINNY_CHUNKED_MAX_M or N % 128 or K % 128:
+        raise ValueError(f"skinny_fp8: unsupported shape M={M} N={N} K={K}")
+    want = (M, N // 2) if epi == SK_SWIGLU else (M, N)
+    if tuple(out.shape) != want:
+        raise ValueError(f"skinny_fp8: out shape {tuple(out.shape)} != {want}")
+    S = splits or skinny_splits(N, K, cus, M)
+    if K % (128 * S):
+        raise ValueError(f"skinny_fp8: K={K} does not split {S} ways in 128-deep steps")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    ws, = _scratch(x.device, stream, "skinny", (S * M * N, SKINNY_MAX_M * 32768, torch.empty, torch.float32))
+    rs = 0
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or row_scale.numel() < M:
+            raise ValueError("skinny_fp8: row_scale must be contiguous float32 [>= M]")
+        rs = row_scale.data_ptr()
+    _native.require_hipops().skinny_gemm_fp8(x.data_ptr(), codes.data_ptr(), col_scale.data_ptr(), out.data_ptr(),
+                                             M, N, K, epi, rs, ws.data_ptr(), S, stream)
+    return out
+
+
+def quantize_rows(w: torch.Tensor):
+    """(codes uint8 [N][K], scale float32 [N]) of the bf16 rows ``w`` on the
+    device kernel -- bit for bit ``ops.quant.quantize_rows_e4m3``."""
+    _check(w, "w")
+    if w.dim() != 2 or w.shape[1] % 8 or not w.shape[1]:
+        raise ValueError("quantize_rows: w must be [N][K], K a positive multiple of 8")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_rows: non-finite weight")
+    N, K = w.shape
+    codes = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    _native.require_hipops().quant_rows_e4m3(w.data_ptr(), N, K, codes.data_ptr(), scale.data_ptr(),
+                                             torch.cuda.current_stream(w.device).cuda_stream)
+    return codes, scale
+
+
+def fp8_decode(codes: torch.Tensor) -> torch.Tensor:
+    """The device decode of e4m3 ``codes`` (uint8, 1-D, a multiple of 4
+    long): int16 bf16 bit patterns, one a code."""
+    if codes.dtype != torch.uint8 or codes.dim() != 1 or codes.numel() % 4 or not codes.is_contiguous():
+        raise ValueError("fp8_decode: codes must be contiguous uint8 [4 n]")
+    out = torch.empty(codes.numel(), dtype=torch.int16, device=codes.device)
+    _native.require_hipops().fp8_decode(codes.data_ptr(), codes.numel(), out.data_ptr(),
+                                        torch.cuda.current_stream(codes.device).cuda_stream)
     return out
 
 

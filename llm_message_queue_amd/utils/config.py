@@ -323,6 +323,7 @@ class BackendConfig:
     micro_stream: str = "partition"    # micro mode: "partition" (own CU partition; the best measured), "high", "same"
     micro_cus: int = 64                # micro partition: CUs of the realtime partition (a multiple of 8)
     micro_gemm: str = "hip"            # micro partition: "hip" (hand-written) or "rocblas" GEMMs
+    micro_weights: str = "bf16"        # micro mode: layer weights of the micro-forwards, "bf16" or "fp8" (W8A16 copy)
     library_gemm: bool = False         # True: hipBLASLt for the sub-wave o / down and small heads
     micro_graph: bool = True           # micro mode: decode micro-forwards replay HIP graphs
     # a forward still incomplete this long after launch = a hung GPU: the
@@ -554,6 +555,10 @@ def validate(cfg: Config) -> Config:
         raise ConfigError("backend.micro_stream must be high, same or partition; micro_slots, micro_inflight >= 1")
     if b.micro_cus % 8 or b.micro_cus < 8 or b.micro_gemm not in ("hip", "rocblas"):
         raise ConfigError("backend.micro_cus must be a positive multiple of 8; micro_gemm hip or rocblas")
+    if b.micro_weights not in ("bf16", "fp8"):
+        raise ConfigError("backend.micro_weights must be bf16 or fp8")
+    if b.micro_weights == "fp8" and b.micro_gemm == "rocblas":
+        raise ConfigError("backend.micro_weights fp8 needs backend.micro_gemm hip")
     fatal = cfg.server.stall_fatal_after
     if fatal > 0 and b.step_timeout > 0 and fatal <= b.step_timeout:
         # a hung forward stops the ticks: the stall watchdog would end the

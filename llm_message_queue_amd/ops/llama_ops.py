@@ -138,15 +138,38 @@ class HipOps:
                        Hq, Hkv, max_ctx, S, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), _stream(qkv))
         return q
 
-    def attention(self, q, kc, vc, pos, slot, Hq, Hkv, scale, out=None):
+    def _attn_args(self, q, kc, vc, Hq, Hkv, out):
+        """Validate what both attention entry points hand to the kernels as
+        raw pointers; returns the output tensor."""
         _check(q, torch.bfloat16, "q")
+        if q.dim() != 2 or q.shape[1] != Hq * 128:
+            raise ValueError("q must be [T, Hq * 128]")
+        _check(kc, torch.bfloat16, "kc")
+        _check(vc, torch.bfloat16, "vc")
+        if kc.dim() != 4 or kc.shape[1] != Hkv or kc.shape[3] != 128 or vc.shape != kc.shape:
+            raise ValueError("kv cache shape mismatch")
+        if kc.device != q.device or vc.device != q.device:
+            raise ValueError("kv cache must be on q's device")
+        if out is None:
+            return torch.empty_like(q)
+        _check(out, torch.bfloat16, "out")
+        if out.shape != q.shape or out.device != q.device:
+            raise ValueError("out must match q's shape and device")
+        return out
+
+    def attention(self, q, kc, vc, pos, slot, Hq, Hkv, scale, out=None):
+        o = self._attn_args(q, kc, vc, Hq, Hkv, out)
+        _check(pos, torch.int32, "pos")
+        _check(slot, torch.int32, "slot")
         T = q.shape[0]
+        if pos.shape != (T,) or slot.shape != (T,):
+            raise ValueError("pos and slot must be [T]")
+        if pos.device != q.device or slot.device != q.device:
+            raise ValueError("pos and slot must be on q's device")
         max_ctx = kc.shape[2]
-        o = out if out is not None else torch.empty_like(q)
         self.k.attention(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), pos.data_ptr(), slot.data_ptr(), T, Hq, Hkv,
                          max_ctx, kc.shape[0], float(scale), o.data_ptr(), _stream(q))
         return o
-
 
     MIXED_ATTENTION = os.environ.get("LLMQ_ATTN_MIXED", "1") != "0"
 
@@ -158,10 +181,11 @@ class HipOps:
         kernel, the rest on the MFMA segment kernel (``seg_keys`` keys per
         block: 32 or 64).  ``mixed`` (default on; env LLMQ_ATTN_MIXED=0
         turns it off): a step with both kinds runs them in ONE launch."""
-        _check(q, torch.bfloat16, "q")
+        o = self._attn_args(q, kc, vc, Hq, Hkv, out)
         if tiles.dtype != torch.int32 or tiles.dim() != 2 or tiles.shape[1] != 4 or not tiles.is_contiguous():
             raise ValueError("tiles must be a contiguous int32 [n, 4] tensor")
-        o = out if out is not None else torch.empty_like(q)
+        if tiles.device != q.device:
+            raise ValueError("tiles must be on q's device")
         self.k.attention_tiles(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), tiles.data_ptr(), tiles.shape[0],
                                int(n_dec), Hq, Hkv, kc.shape[2], kc.shape[0], q.shape[0], float(scale),
                                o.data_ptr(), _stream(q), int(seg_keys),

@@ -502,23 +502,28 @@ static void kv_move(uintptr_t table, int layers, int slots, int slot, int n, int
 // ---------------------------------------------------------------------- skinny GEMM (M <= SK_MAX_M)
 // C (+)= A . W^T for the small steps (skinny_kernels.h): split-K partials into
 // ws [S][M][N] fp32, then the finalize kernel (row scale, epilogue, bf16).
-static void skinny_gemm(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, int epi, uintptr_t rs,
-                        uintptr_t ws, int nsplit, uintptr_t stream) {
-  require(M >= 1 && M <= SK_MAX_M, "skinny_gemm: M must be in [1, SK_MAX_M]");
-  require(N % SK_NB == 0, "skinny_gemm: N must be a multiple of 128");
-  require(nsplit >= 1 && K % (SK_KS * nsplit) == 0, "skinny_gemm: K must be a multiple of 128 * S");
-  require(epi == SK_EPI_STORE || epi == SK_EPI_RESID || epi == SK_EPI_SWIGLU, "skinny_gemm: unknown epilogue");
-  require(epi != SK_EPI_SWIGLU || N % 256 == 0, "skinny_gemm: SwiGLU needs N % 256 == 0");
-  require(a % 16 == 0 && w % 16 == 0 && c % 16 == 0 && ws % 16 == 0 && ws != 0, "skinny_gemm: alignment");
-  require((int64_t)N * K < (int64_t)1 << 31, "skinny_gemm: weight too large");
+// FP8: w = e4m3 weight codes [N][K] bytes and cs = their fp32 column scales
+// [N] (skinny_partial_kernel<MT, true>, skinny_finalize_cs_kernel).
+template <bool FP8>
+static void skinny_launch(const char* fn, uintptr_t a, uintptr_t w, uintptr_t cs, uintptr_t c, int M, int N, int K,
+                          int epi, uintptr_t rs, uintptr_t ws, int nsplit, uintptr_t stream) {
+  require_in(fn, M >= 1 && M <= SK_MAX_M, "M must be in [1, SK_MAX_M]");
+  require_in(fn, N % SK_NB == 0, "N must be a multiple of 128");
+  require_in(fn, nsplit >= 1 && K % (SK_KS * nsplit) == 0, "K must be a multiple of 128 * S");
+  require_in(fn, epi == SK_EPI_STORE || epi == SK_EPI_RESID || epi == SK_EPI_SWIGLU, "unknown epilogue");
+  require_in(fn, epi != SK_EPI_SWIGLU || N % 256 == 0, "SwiGLU needs N % 256 == 0");
+  require_in(fn, a % 16 == 0 && w % 16 == 0 && c % 16 == 0 && ws % 16 == 0 && ws != 0, "alignment");
+  if constexpr (FP8) require_in(fn, cs % 16 == 0 && cs != 0, "alignment");
+  require_in(fn, (int64_t)N * K < (int64_t)1 << 31, "weight too large");
   const int nm = (M + 127) / 128;                   // 128-row chunks of A (M > 128)
   const int mt = nm > 1 ? 8 : (M + 15) / 16;
   const dim3 grid(N / SK_NB * nm, nsplit);
   const int kc = K / nsplit;
   auto* A_ = P<const uint16_t>(a);
-  auto* W_ = P<const uint16_t>(w);
+  auto* W_ = P<const typename SkW<FP8>::elem>(w);
   auto* ws_ = P<float>(ws);
-#define SK_LAUNCH(T) hipLaunchKernelGGL(skinny_partial_kernel<T>, grid, dim3(256), 0, S(stream), A_, W_, ws_, M, N, K, kc, nm)
+#define SK_LAUNCH(T) \
+  hipLaunchKernelGGL((skinny_partial_kernel<T, FP8>), grid, dim3(256), 0, S(stream), A_, W_, ws_, M, N, K, kc, nm)
   switch (mt) {
     case 1: SK_LAUNCH(1); break;
     case 2: SK_LAUNCH(2); break;
@@ -532,64 +537,34 @@ static void skinny_gemm(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int
 #undef SK_LAUNCH
   check_launch();
   const int nout = epi == SK_EPI_SWIGLU ? N / 2 : N;
-  const int threads = M * (nout / 4);
-  const dim3 fgrid((threads + 255) / 256);
+  const dim3 fgrid((M * (nout / 4) + 255) / 256);
   const float* rs_ = rs ? P<const float>(rs) : nullptr;
   auto* C_ = P<uint16_t>(c);
+  auto finalize = [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if constexpr (FP8)
+      hipLaunchKernelGGL(skinny_finalize_cs_kernel<EPI>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_,
+                         P<const float>(cs), C_);
+    else
+      hipLaunchKernelGGL(skinny_finalize_kernel<EPI>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, C_);
+  };
   if (epi == SK_EPI_STORE)
-    hipLaunchKernelGGL(skinny_finalize_kernel<SK_EPI_STORE>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, C_);
+    finalize(std::integral_constant<int, SK_EPI_STORE>{});
   else if (epi == SK_EPI_RESID)
-    hipLaunchKernelGGL(skinny_finalize_kernel<SK_EPI_RESID>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, C_);
+    finalize(std::integral_constant<int, SK_EPI_RESID>{});
   else
-    hipLaunchKernelGGL(skinny_finalize_kernel<SK_EPI_SWIGLU>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, C_);
+    finalize(std::integral_constant<int, SK_EPI_SWIGLU>{});
   check_launch();
 }
 
-// The same with e4m3 weight codes wq [N][K] bytes and fp32 column scales cs [N]
-// (skinny_partial_fp8_kernel, skinny_finalize_cs_kernel).
+static void skinny_gemm(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, int epi, uintptr_t rs,
+                        uintptr_t ws, int nsplit, uintptr_t stream) {
+  skinny_launch<false>("skinny_gemm", a, w, 0, c, M, N, K, epi, rs, ws, nsplit, stream);
+}
+
 static void skinny_gemm_fp8(uintptr_t a, uintptr_t wq, uintptr_t cs, uintptr_t c, int M, int N, int K, int epi,
                             uintptr_t rs, uintptr_t ws, int nsplit, uintptr_t stream) {
-  require(M >= 1 && M <= SK_MAX_M, "skinny_gemm_fp8: M must be in [1, SK_MAX_M]");
-  require(N % SK_NB == 0, "skinny_gemm_fp8: N must be a multiple of 128");
-  require(nsplit >= 1 && K % (SK_KS * nsplit) == 0, "skinny_gemm_fp8: K must be a multiple of 128 * S");
-  require(epi == SK_EPI_STORE || epi == SK_EPI_RESID || epi == SK_EPI_SWIGLU, "skinny_gemm_fp8: unknown epilogue");
-  require(epi != SK_EPI_SWIGLU || N % 256 == 0, "skinny_gemm_fp8: SwiGLU needs N % 256 == 0");
-  require(a % 16 == 0 && wq % 16 == 0 && cs % 16 == 0 && cs != 0 && c % 16 == 0 && ws % 16 == 0 && ws != 0,
-          "skinny_gemm_fp8: alignment");
-  require((int64_t)N * K < (int64_t)1 << 31, "skinny_gemm_fp8: weight too large");
-  const int nm = (M + 127) / 128;
-  const int mt = nm > 1 ? 8 : (M + 15) / 16;
-  const dim3 grid(N / SK_NB * nm, nsplit);
-  const int kc = K / nsplit;
-  auto* A_ = P<const uint16_t>(a);
-  auto* W_ = P<const uint8_t>(wq);
-  auto* ws_ = P<float>(ws);
-#define SKQ_LAUNCH(T) \
-  hipLaunchKernelGGL(skinny_partial_fp8_kernel<T>, grid, dim3(256), 0, S(stream), A_, W_, ws_, M, N, K, kc, nm)
-  switch (mt) {
-    case 1: SKQ_LAUNCH(1); break;
-    case 2: SKQ_LAUNCH(2); break;
-    case 3: SKQ_LAUNCH(3); break;
-    case 4: SKQ_LAUNCH(4); break;
-    case 5: SKQ_LAUNCH(5); break;
-    case 6: SKQ_LAUNCH(6); break;
-    case 7: SKQ_LAUNCH(7); break;
-    default: SKQ_LAUNCH(8); break;
-  }
-#undef SKQ_LAUNCH
-  check_launch();
-  const int nout = epi == SK_EPI_SWIGLU ? N / 2 : N;
-  const dim3 fgrid((M * (nout / 4) + 255) / 256);
-  const float* rs_ = rs ? P<const float>(rs) : nullptr;
-  const float* cs_ = P<const float>(cs);
-  auto* C_ = P<uint16_t>(c);
-  if (epi == SK_EPI_STORE)
-    hipLaunchKernelGGL(skinny_finalize_cs_kernel<SK_EPI_STORE>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, cs_, C_);
-  else if (epi == SK_EPI_RESID)
-    hipLaunchKernelGGL(skinny_finalize_cs_kernel<SK_EPI_RESID>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, cs_, C_);
-  else
-    hipLaunchKernelGGL(skinny_finalize_cs_kernel<SK_EPI_SWIGLU>, fgrid, dim3(256), 0, S(stream), ws_, nsplit, M, N, rs_, cs_, C_);
-  check_launch();
+  skinny_launch<true>("skinny_gemm_fp8", a, wq, cs, c, M, N, K, epi, rs, ws, nsplit, stream);
 }
 
 // codes [N][K] e4m3 + scale [N] fp32 of the bf16 rows w [N][K] (ops/quant.py)

@@ -1,34 +1,45 @@
-// Skinny GEMMs for small steps (M <= 64 rows, up to 256 in 64-row chunks): C = A[M][K] . W[N][K]^T with
-// the realtime micro-forwards' epilogues (store, residual add, SwiGLU over the
-// permuted gate/up weight, optional per-row RMSNorm scale).
+// Skinny GEMMs for small steps (M <= 64 rows, up to 1024 in 128-row chunks):
+// C = A[M][K] . W[N][K]^T with the realtime micro-forwards' epilogues (store,
+// residual add, SwiGLU over the permuted gate/up weight, optional per-row
+// RMSNorm scale).  One partial kernel, two weight formats: bf16, or FP8 (e4m3)
+// codes with one fp32 scale a weight row (W8A16; ops/quant.py holds the
+// contract); A is bf16 in both.
 //
 // Why a second GEMM: at M <= 64 the 256x256-tile kernel (gemm_kernels.h)
 // computes 4x the useful MFMA work per tile and a 16-tile N = 4096 product
 // leaves most CUs of even a 32-CU partition idle, so a micro-forward ran at
 // ~0.42 TB/s of weight traffic (profiles/r6_realtime_modes.md).  A small step
-// is a stream over the weights: this kernel reads every weight byte once with
-// 64 contiguous bytes a lane (256 B a weight row per four lanes), keeps the
-// whole M in one block (MT 16-row MFMA fragments), keeps two 128-deep steps
-// of weight loads in flight behind the one it computes, and splits K when
-// the column blocks alone cannot fill the CUs.
+// is a stream over the weights: this kernel reads every weight byte once in
+// contiguous runs, keeps a chunk's whole M in one block (MT 16-row MFMA
+// fragments), keeps 256 bytes a lane a fragment of weight loads in flight
+// behind the step it computes, and splits K when the column blocks alone
+// cannot fill the CUs.
 //
 // Layout.  A block = 4 waves = 128 output columns x a K range; wave w owns
 // columns [32w, 32w + 32) as two 16-column fragments.  K is walked 128 at a
 // time in a PERMUTED order: MFMA step s4 of lane (fr, fq) takes the K chunk
 // (fq * 4 + s4) * 8 for BOTH operands, so each lane's weight read for the
-// 128-deep step is one contiguous 64-byte run and the sum over K is unchanged
-// (the same permutation on both sides).  A[0:M][k:k+128] is staged in LDS
-// (double buffered, rows padded by 16 B) and read as MFMA A fragments; the
-// weight fragments come straight from global memory into a ring of three
-// register stages, two 128-deep steps ahead.
+// 128-deep step is one contiguous run of 32 elements and the sum over K is
+// unchanged (the same permutation on both sides).  A[0:M][k:k+128] is staged
+// in LDS (double buffered, rows padded by 16 B) and read as MFMA A fragments;
+// the weight fragments come straight from global memory into a ring of
+// register stages (SkW):
+//   bf16: 64-byte runs (256 B a weight row per four lanes), three stages of
+//         4 x 16 B, two steps of loads behind the one computed: 96 registers;
+//   fp8:  32-byte runs (a weight row's 128 bytes = one cache line per four
+//         lanes), half the bf16 ones, so five stages of 2 x 16 B, four steps
+//         behind: the same 256 bytes in flight in 80 registers.  The codes
+//         are decoded to bf16 in registers right before the bf16 MFMA (every
+//         finite code is exactly a bf16 number), so the arithmetic is the
+//         bf16 kernel's on the decoded weights and the row's scale waits for
+//         the finalize kernel.
 //
 // Split-K partials are written to ws[S][M][N] fp32 and summed in split
 // order by the finalize kernel (deterministic: no atomics), which applies
-// the row scale and the epilogue and writes bf16.
+// the column scale (fp8), the row scale and the epilogue and writes bf16.
 //
-// The second half of the file is the same GEMM over FP8 (e4m3) weight codes
-// with one fp32 scale a weight row (W8A16), the quantiser that makes them and
-// the decode both use.
+// The end of the file is the quantiser that makes the codes and the decode
+// the tests use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,10 +64,36 @@ enum { SK_EPI_STORE = 0, SK_EPI_RESID = 1, SK_EPI_SWIGLU = 2 };
 // chunk fastest within the XCD's share) and the repeats come from its L2.
 constexpr int SK_MAX_M = 1024;           // up to 8 chunks (o / down at mid-size steps)
 
-template <int MT>
+// fp8 (e4m3) -> bf16: bytes 2 HI, 2 HI + 1 of w -> two bf16 (low half first): the scaled pack
+// conversion with scale 1, one VALU op a pair.  (v_cvt_pk_f32_fp8 + packing
+// the two high halves measured 0-7 % slower per GEMM: profiles/skinny_fp8.md.)
+template <bool HI>
+__device__ __forceinline__ uint32_t sk_fp8x2_bf16(uint32_t w) {
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+}
+
+__device__ __forceinline__ sk_bf16x8 sk_fp8x8_bf16(uint32_t lo, uint32_t hi) {
+  const sk_u32x4 r = {sk_fp8x2_bf16<false>(lo), sk_fp8x2_bf16<true>(lo), sk_fp8x2_bf16<false>(hi),
+                      sk_fp8x2_bf16<true>(hi)};
+  return __builtin_bit_cast(sk_bf16x8, r);
+}
+
+// The weight format of skinny_partial_kernel: the element type, the register
+// stages ST of the ring and the 16-byte loads NV of a stage (a lane's run of a
+// 128-deep step), for two fragments.  ST * NV * 16 = 256 bytes (the header).
+template <bool FP8>
+struct SkW {
+  using elem = std::conditional_t<FP8, uint8_t, uint16_t>;
+  static constexpr int ST = FP8 ? 5 : 3;
+  static constexpr int NV = FP8 ? 2 : 4;
+};
+
+template <int MT, bool FP8>
 __global__ void __launch_bounds__(256)
-skinny_partial_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, float* __restrict__ ws,
-                      int M, int N, int K, int kc, int nm) {
+skinny_partial_kernel(const uint16_t* __restrict__ A, const typename SkW<FP8>::elem* __restrict__ W,
+                      float* __restrict__ ws, int M, int N, int K, int kc, int nm) {
+  using elem = typename SkW<FP8>::elem;
+  constexpr int ST = SkW<FP8>::ST, NV = SkW<FP8>::NV;
   __shared__ __align__(16) uint16_t As[2][MT * 16][SK_LDA];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
@@ -77,9 +114,9 @@ skinny_partial_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict
   const int n0 = cb * SK_NB + w * 32;
   const int kb = blockIdx.y * kc;
   const int nsteps = kc / SK_KS;
-  // weight rows of this lane's two fragments; K offset of its 64-byte run
-  const uint16_t* wp0 = W + (size_t)(n0 + fr) * K + kb + fq * 32;
-  const uint16_t* wp1 = wp0 + (size_t)16 * K;
+  // weight rows of this lane's two fragments; K offset of its 32-element run
+  const elem* wp0 = W + (size_t)(n0 + fr) * K + kb + fq * 32;
+  const elem* wp1 = wp0 + (size_t)16 * K;
   // A staging: thread t -> row g * 64 + t / 4 of each 64-row group g,
   // chunks (t % 4) * 4 .. + 3 (16 B each)
   constexpr int RG = (MT * 16 + 63) / 64;
@@ -100,19 +137,19 @@ skinny_partial_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict
     acc[m][0] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
     acc[m][1] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  // weight fragments in a ring of three register stages: step k computes
-  // from stage k % 3 while steps k + 1 and k + 2 are in flight (64 B a lane
-  // a fragment a step: enough bytes outstanding per CU to stream the weights
-  // at the partition's bandwidth); the stage index is compile-time below
-  sk_u32x4 wb[3][2][4];
+  // weight fragments in a ring of ST register stages: step k computes from
+  // stage k % ST while steps k + 1 .. k + ST - 1 are in flight (256 B a lane
+  // a fragment: enough bytes outstanding per CU to stream the weights at the
+  // partition's bandwidth); the stage index is compile-time below
+  sk_u32x4 wb[ST][2][NV];
   sk_u32x4 ab[RG][4];
   auto load_w = [&](auto stc, int step) {
-    constexpr int ST = decltype(stc)::value;
+    constexpr int S = decltype(stc)::value, EV = 16 / sizeof(elem);   // elements a 16-byte load
     const int ko = step * SK_KS;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      wb[ST][0][i] = *reinterpret_cast<const sk_u32x4*>(wp0 + ko + 8 * i);
-      wb[ST][1][i] = *reinterpret_cast<const sk_u32x4*>(wp1 + ko + 8 * i);
+    for (int i = 0; i < NV; ++i) {
+      wb[S][0][i] = *reinterpret_cast<const sk_u32x4*>(wp0 + ko + EV * i);
+      wb[S][1][i] = *reinterpret_cast<const sk_u32x4*>(wp1 + ko + EV * i);
     }
   };
   auto load_a = [&](int step) {
@@ -133,18 +170,25 @@ skinny_partial_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict
       }
     }
   };
-  // one 128-deep step from register stage CUR (= step % 3) and A buffer
-  // step % 2; the weights of step + 2 and the A tile of step + 1 load meanwhile
+  // one 128-deep step from register stage CUR (= step % ST) and A buffer
+  // step % 2; the weights of step + ST - 1 and the A tile of step + 1 load
+  // meanwhile
   auto run_step = [&](auto curc, int step) {
     constexpr int CUR = decltype(curc)::value;
-    if (step + 2 < nsteps) load_w(std::integral_constant<int, (CUR + 2) % 3>{}, step + 2);
+    if (step + ST - 1 < nsteps) load_w(std::integral_constant<int, (CUR + ST - 1) % ST>{}, step + ST - 1);
     const bool more = step + 1 < nsteps;
     if (more) load_a(step + 1);
     const int abuf = step & 1;
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
-      const sk_bf16x8 b0 = __builtin_bit_cast(sk_bf16x8, wb[CUR][0][s4]);
-      const sk_bf16x8 b1 = __builtin_bit_cast(sk_bf16x8, wb[CUR][1][s4]);
+      sk_bf16x8 b0, b1;
+      if constexpr (FP8) {   // K chunk s4 of the run: bytes 8 s4 .. 8 s4 + 7
+        b0 = sk_fp8x8_bf16(wb[CUR][0][s4 >> 1][(s4 & 1) * 2], wb[CUR][0][s4 >> 1][(s4 & 1) * 2 + 1]);
+        b1 = sk_fp8x8_bf16(wb[CUR][1][s4 >> 1][(s4 & 1) * 2], wb[CUR][1][s4 >> 1][(s4 & 1) * 2 + 1]);
+      } else {
+        b0 = __builtin_bit_cast(sk_bf16x8, wb[CUR][0][s4]);
+        b1 = __builtin_bit_cast(sk_bf16x8, wb[CUR][1][s4]);
+      }
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         const sk_bf16x8 a = *reinterpret_cast<const sk_bf16x8*>(&As[abuf][m * 16 + fr][(fq * 4 + s4) * 8]);
@@ -159,12 +203,22 @@ skinny_partial_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict
   load_a(0);
   load_w(std::integral_constant<int, 0>{}, 0);
   if (nsteps > 1) load_w(std::integral_constant<int, 1>{}, 1);
+  if constexpr (ST > 3) {
+    if (nsteps > 2) load_w(std::integral_constant<int, 2>{}, 2);
+    if (nsteps > 3) load_w(std::integral_constant<int, 3>{}, 3);
+  }
   store_a(0);
   __syncthreads();
-  for (int step = 0; step < nsteps; step += 3) {
+  // (written out, not folded over the stages: a generic unroll changed the
+  // instructions of every instantiation -- profiles/skinny_merge.md)
+  for (int step = 0; step < nsteps; step += ST) {
     run_step(std::integral_constant<int, 0>{}, step);
     if (step + 1 < nsteps) run_step(std::integral_constant<int, 1>{}, step + 1);
     if (step + 2 < nsteps) run_step(std::integral_constant<int, 2>{}, step + 2);
+    if constexpr (ST > 3) {
+      if (step + 3 < nsteps) run_step(std::integral_constant<int, 3>{}, step + 3);
+      if (step + 4 < nsteps) run_step(std::integral_constant<int, 4>{}, step + 4);
+    }
   }
   // partials: lane -> column n0 + j * 16 + fr, rows m * 16 + fq * 4 + e
   float* out = ws + (size_t)blockIdx.y * M * N;
@@ -259,29 +313,6 @@ skinny_finalize_cs_kernel(const float* __restrict__ ws, int S, int M, int N, con
   sk_finalize<EPI, true>(ws, S, M, N, rs, cs, C);
 }
 
-// ---------------------------------------------------------------------- fp8 (e4m3) weights, W8A16
-// The weights as OCP e4m3fn codes (one byte an element, [N][K]) with one fp32
-// scale a row (ops/quant.py holds the contract); A stays bf16.  The codes are
-// decoded to bf16 in registers right before the bf16 MFMA (every finite code
-// is exactly a bf16 number), so the arithmetic is skinny_partial_kernel's on
-// the decoded weights and the row's scale waits for the finalize kernel.
-
-typedef __attribute__((ext_vector_type(2))) __bf16 sk_bf16x2;
-
-// bytes 2 HI, 2 HI + 1 of w -> two bf16 (low half first): the scaled pack
-// conversion with scale 1, one VALU op a pair.  (v_cvt_pk_f32_fp8 + packing
-// the two high halves measured 0-7 % slower per GEMM: profiles/skinny_fp8.md.)
-template <bool HI>
-__device__ __forceinline__ uint32_t sk_fp8x2_bf16(uint32_t w) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
-
-__device__ __forceinline__ sk_bf16x8 sk_fp8x8_bf16(uint32_t lo, uint32_t hi) {
-  const sk_u32x4 r = {sk_fp8x2_bf16<false>(lo), sk_fp8x2_bf16<true>(lo), sk_fp8x2_bf16<false>(hi),
-                      sk_fp8x2_bf16<true>(hi)};
-  return __builtin_bit_cast(sk_bf16x8, r);
-}
-
 // out[i] = bf16 bits of the code in byte i % 4 of in[i / 4]: the GEMM's decode, for tests
 __global__ void __launch_bounds__(256) fp8_decode_kernel(const uint32_t* __restrict__ in, int n,
                                                          uint16_t* __restrict__ out) {
@@ -290,141 +321,6 @@ __global__ void __launch_bounds__(256) fp8_decode_kernel(const uint32_t* __restr
   const uint32_t w = in[i >> 2];
   const uint32_t p = (i & 2) ? sk_fp8x2_bf16<true>(w) : sk_fp8x2_bf16<false>(w);
   out[i] = (uint16_t)((i & 1) ? p >> 16 : p);
-}
-
-constexpr int SKQ_ST = 5;           // register stages of the fp8 weight ring
-
-// skinny_partial_kernel with Wq = e4m3 codes [N][K].  Same blocks, chunks of
-// M, 128-deep steps and K permutation: MFMA step s4 of lane (fr, fq) takes K
-// chunk (fq * 4 + s4) * 8, which for byte weights makes a lane's read of a
-// step one contiguous 32-byte run (a weight row's 128 bytes = one cache line
-// per four lanes).  The runs are half the bf16 kernel's, so the ring is
-// SKQ_ST = 5 stages deep -- four steps of loads behind the one computed, the
-// same 256 bytes a lane a fragment in flight -- in 80 registers (bf16: 96).
-template <int MT>
-__global__ void __launch_bounds__(256)
-skinny_partial_fp8_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq, float* __restrict__ ws,
-                          int M, int N, int K, int kc, int nm) {
-  __shared__ __align__(16) uint16_t As[2][MT * 16][SK_LDA];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int ncb = N / SK_NB;
-  int cb = blockIdx.x, mc = 0;
-  if (nm > 1) {
-    if ((ncb & 7) == 0) {
-      const int b = blockIdx.x, idx = b >> 3;
-      cb = (idx / nm) * 8 + (b & 7);
-      mc = idx % nm;
-    } else {
-      cb = blockIdx.x / nm;
-      mc = blockIdx.x % nm;
-    }
-  }
-  const int m0 = mc * (MT * 16);
-  const int Ml = min(M - m0, MT * 16);
-  const int n0 = cb * SK_NB + w * 32;
-  const int kb = blockIdx.y * kc;
-  const int nsteps = kc / SK_KS;
-  // weight rows of this lane's two fragments; byte offset of its 32-byte run
-  const uint8_t* wp0 = Wq + (size_t)(n0 + fr) * K + kb + fq * 32;
-  const uint8_t* wp1 = wp0 + (size_t)16 * K;
-  constexpr int RG = (MT * 16 + 63) / 64;
-  const int arow = tid >> 2, acb = (tid & 3) * 4;
-  bool a_on[RG], a_live[RG];
-  const uint16_t* ap[RG];
-#pragma unroll
-  for (int g = 0; g < RG; ++g) {
-    const int r = g * 64 + arow;
-    a_on[g] = r < MT * 16;
-    a_live[g] = a_on[g] && r < Ml;
-    ap[g] = A + (size_t)(m0 + (a_live[g] ? r : 0)) * K + kb + acb * 8;
-  }
-
-  sk_f32x4 acc[MT][2];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    acc[m][0] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
-    acc[m][1] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  // stage k % SKQ_ST holds step k: [fragment][16-byte half of the run]
-  sk_u32x4 wb[SKQ_ST][2][2];
-  sk_u32x4 ab[RG][4];
-  auto load_w = [&](auto stc, int step) {
-    constexpr int ST = decltype(stc)::value;
-    const int ko = step * SK_KS;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      wb[ST][0][i] = *reinterpret_cast<const sk_u32x4*>(wp0 + ko + 16 * i);
-      wb[ST][1][i] = *reinterpret_cast<const sk_u32x4*>(wp1 + ko + 16 * i);
-    }
-  };
-  auto load_a = [&](int step) {
-    const int ko = step * SK_KS;
-#pragma unroll
-    for (int g = 0; g < RG; ++g)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        ab[g][i] = a_live[g] ? *reinterpret_cast<const sk_u32x4*>(ap[g] + ko + 8 * i) : sk_u32x4{0u, 0u, 0u, 0u};
-  };
-  auto store_a = [&](int buf) {
-#pragma unroll
-    for (int g = 0; g < RG; ++g) {
-      if (a_on[g]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          *reinterpret_cast<sk_u32x4*>(&As[buf][g * 64 + arow][(acb + i) * 8]) = ab[g][i];
-      }
-    }
-  };
-  // one step from register stage CUR (= step % SKQ_ST) and A buffer step % 2;
-  // the codes of step + SKQ_ST - 1 and the A tile of step + 1 load meanwhile
-  auto run_step = [&](auto curc, int step) {
-    constexpr int CUR = decltype(curc)::value;
-    if (step + SKQ_ST - 1 < nsteps)
-      load_w(std::integral_constant<int, (CUR + SKQ_ST - 1) % SKQ_ST>{}, step + SKQ_ST - 1);
-    const bool more = step + 1 < nsteps;
-    if (more) load_a(step + 1);
-    const int abuf = step & 1;
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      // K chunk s4 of the run: bytes 8 s4 .. 8 s4 + 7
-      const sk_bf16x8 b0 = sk_fp8x8_bf16(wb[CUR][0][s4 >> 1][(s4 & 1) * 2], wb[CUR][0][s4 >> 1][(s4 & 1) * 2 + 1]);
-      const sk_bf16x8 b1 = sk_fp8x8_bf16(wb[CUR][1][s4 >> 1][(s4 & 1) * 2], wb[CUR][1][s4 >> 1][(s4 & 1) * 2 + 1]);
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const sk_bf16x8 a = *reinterpret_cast<const sk_bf16x8*>(&As[abuf][m * 16 + fr][(fq * 4 + s4) * 8]);
-        acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b0, acc[m][0], 0, 0, 0);
-        acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b1, acc[m][1], 0, 0, 0);
-      }
-    }
-    if (more) store_a(abuf ^ 1);
-    __syncthreads();
-  };
-
-  load_a(0);
-  load_w(std::integral_constant<int, 0>{}, 0);
-  if (nsteps > 1) load_w(std::integral_constant<int, 1>{}, 1);
-  if (nsteps > 2) load_w(std::integral_constant<int, 2>{}, 2);
-  if (nsteps > 3) load_w(std::integral_constant<int, 3>{}, 3);
-  store_a(0);
-  __syncthreads();
-  for (int step = 0; step < nsteps; step += SKQ_ST) {
-    run_step(std::integral_constant<int, 0>{}, step);
-    if (step + 1 < nsteps) run_step(std::integral_constant<int, 1>{}, step + 1);
-    if (step + 2 < nsteps) run_step(std::integral_constant<int, 2>{}, step + 2);
-    if (step + 3 < nsteps) run_step(std::integral_constant<int, 3>{}, step + 3);
-    if (step + 4 < nsteps) run_step(std::integral_constant<int, 4>{}, step + 4);
-  }
-  float* out = ws + (size_t)blockIdx.y * M * N;
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int row = m * 16 + fq * 4 + e;
-        if (row < Ml) out[(size_t)(m0 + row) * N + n0 + j * 16 + fr] = acc[m][j][e];
-      }
 }
 
 // Rows of bf16 weights -> e4m3 codes + one power-of-two scale a row, bit for

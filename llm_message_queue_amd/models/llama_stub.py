@@ -339,15 +339,13 @@ class LlamaStub:
 
         scale = None                                     # row scales of res from the previous down GEMM
         for i, L in enumerate(layers):
-            if quant:
+            if quant or skinny:
                 qkv = torch.empty((T, L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
-                G.skinny_fp8(res, *L["fp8"]["wqkv"], qkv, G.SK_STORE, row_scale=ops.row_rms(res, cfg.eps),
-                             cus=sk_cus or 32)
-                q = ops.rope_kv(qkv, pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i],
-                                self.vcache[i])
-            elif skinny:
-                qkv = torch.empty((T, L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
-                G.skinny(res, L["wqkv"], qkv, G.SK_STORE, row_scale=ops.row_rms(res, cfg.eps), cus=sk_cus)
+                rs = ops.row_rms(res, cfg.eps)
+                if quant:
+                    G.skinny_fp8(res, *L["fp8"]["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=sk_cus or 32)
+                else:
+                    G.skinny(res, L["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=sk_cus)
                 q = ops.rope_kv(qkv, pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i],
                                 self.vcache[i])
             elif rows_qkv and self.row_scale_norm:

@@ -384,6 +384,32 @@ def skinny_splits(N: int, K: int, cus: int, M: int = 1) -> int:
     return best
 
 
+def _skinny_args(fn: str, x: torch.Tensor, wshape, out: torch.Tensor, epi: int, row_scale, cus: int, splits: int):
+    """What :func:`skinny` and :func:`skinny_fp8` (``fn``, for the messages)
+    share once their operands are checked: the shapes against the weight's
+    ``wshape`` [N][K], the split-K factor, the scratch and the row scale.
+    Returns the launch's ``(M, N, K, epi, row-scale pointer, scratch pointer,
+    S, stream)``."""
+    M, K = x.shape
+    N = wshape[0]
+    if wshape[1] != K or not 1 <= M <= SKINNY_CHUNKED_MAX_M or N % 128 or K % 128:
+        raise ValueError(f"{fn}: unsupported shape M={M} N={N} K={K}")
+    want = (M, N // 2) if epi == SK_SWIGLU else (M, N)
+    if tuple(out.shape) != want:
+        raise ValueError(f"{fn}: out shape {tuple(out.shape)} != {want}")
+    S = splits or skinny_splits(N, K, cus, M)
+    if K % (128 * S):
+        raise ValueError(f"{fn}: K={K} does not split {S} ways in 128-deep steps")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    ws, = _scratch(x.device, stream, "skinny", (S * M * N, SKINNY_MAX_M * 32768, torch.empty, torch.float32))
+    rs = 0
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or row_scale.numel() < M:
+            raise ValueError(f"{fn}: row_scale must be contiguous float32 [>= M]")
+        rs = row_scale.data_ptr()
+    return M, N, K, epi, rs, ws.data_ptr(), S, stream
+
+
 def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_scale=None, cus: int = 32,
            splits: int = 0):
     """``out`` (+)= ``x`` [M <= 1024][K] . ``w`` [N][K]^T on the skinny kernel
@@ -395,25 +421,8 @@ def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_sc
     _check(x, "x")
     _check(w, "w")
     _check(out, "out")
-    M, K = x.shape
-    N = w.shape[0]
-    if w.shape[1] != K or not 1 <= M <= SKINNY_CHUNKED_MAX_M or N % 128 or K % 128:
-        raise ValueError(f"skinny: unsupported shape M={M} N={N} K={K}")
-    want = (M, N // 2) if epi == SK_SWIGLU else (M, N)
-    if tuple(out.shape) != want:
-        raise ValueError(f"skinny: out shape {tuple(out.shape)} != {want}")
-    S = splits or skinny_splits(N, K, cus, M)
-    if K % (128 * S):
-        raise ValueError(f"skinny: K={K} does not split {S} ways in 128-deep steps")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    ws, = _scratch(x.device, stream, "skinny", (S * M * N, SKINNY_MAX_M * 32768, torch.empty, torch.float32))
-    rs = 0
-    if row_scale is not None:
-        if row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or row_scale.numel() < M:
-            raise ValueError("skinny: row_scale must be contiguous float32 [>= M]")
-        rs = row_scale.data_ptr()
-    _native.require_hipops().skinny_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, epi, rs,
-                                         ws.data_ptr(), S, stream)
+    args = _skinny_args("skinny", x, w.shape, out, epi, row_scale, cus, splits)
+    _native.require_hipops().skinny_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), *args)
     return out
 
 
@@ -430,30 +439,15 @@ def skinny_fp8(x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, ou
     _check(out, "out")
     if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous() or codes.data_ptr() % 16:
         raise ValueError("skinny_fp8: codes must be contiguous 16-byte-aligned uint8 [N][K]")
-    M, K = x.shape
     N = codes.shape[0]
     if col_scale.dtype != torch.float32 or tuple(col_scale.shape) != (N,) or not col_scale.is_contiguous() \
             or col_scale.data_ptr() % 16:
         raise ValueError("skinny_fp8: col_scale must be contiguous 16-byte-aligned float32 [N]")
     if codes.device != x.device or col_scale.device != x.device:
         raise ValueError("skinny_fp8: codes / col_scale must be on x's device")
-    if codes.shape[1] != K or not 1 <= M <= SKINNY_CHUNKED_MAX_M or N % 128 or K % 128:
-        raise ValueError(f"skinny_fp8: unsupported shape M={M} N={N} K={K}")
-    want = (M, N // 2) if epi == SK_SWIGLU else (M, N)
-    if tuple(out.shape) != want:
-        raise ValueError(f"skinny_fp8: out shape {tuple(out.shape)} != {want}")
-    S = splits or skinny_splits(N, K, cus, M)
-    if K % (128 * S):
-        raise ValueError(f"skinny_fp8: K={K} does not split {S} ways in 128-deep steps")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    ws, = _scratch(x.device, stream, "skinny", (S * M * N, SKINNY_MAX_M * 32768, torch.empty, torch.float32))
-    rs = 0
-    if row_scale is not None:
-        if row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or row_scale.numel() < M:
-            raise ValueError("skinny_fp8: row_scale must be contiguous float32 [>= M]")
-        rs = row_scale.data_ptr()
+    args = _skinny_args("skinny_fp8", x, codes.shape, out, epi, row_scale, cus, splits)
     _native.require_hipops().skinny_gemm_fp8(x.data_ptr(), codes.data_ptr(), col_scale.data_ptr(), out.data_ptr(),
-                                             M, N, K, epi, rs, ws.data_ptr(), S, stream)
+                                             *args)
     return out
 
 

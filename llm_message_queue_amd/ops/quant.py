@@ -1,5 +1,5 @@
 """Host twin of the FP8 weight quantisation (``csrc/kernels/skinny_kernels.h``:
-``quant_rows_e4m3_kernel``, the decode of ``skinny_partial_fp8_kernel``).
+``quant_rows_e4m3_kernel``, the decode of ``skinny_partial_kernel<MT, true>``).
 
 Contract.  A weight matrix ``w`` [N][K] becomes one byte an element plus one
 float32 scale a row (= an output channel of ``x . wᵀ``):

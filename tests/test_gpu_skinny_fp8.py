@@ -138,6 +138,26 @@ def test_skinny_fp8_equals_the_bf16_kernel_on_decoded_weights():
     assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("M", [m for mt in range(1, 9) for m in (16 * mt - 1, 16 * mt)])
+def test_skinny_every_fragment_count_on_both_formats(M):
+    """The launcher's dispatch over MT = 1 .. 8 row fragments (M = 16 MT - 1
+    and 16 MT), on both weight formats: two column blocks and six pipeline
+    steps without split-K, so the three- and the five-stage ring both wrap.
+    The fp8 kernel equals the bf16 kernel on the decoded weights (power-of-two
+    scales, as above), and that one holds the fp32 product's bound."""
+    x, codes, cs = _rand_q(M, 768, 256, seed=M, pow2=True)
+    w = Q.dequantize(codes, cs)
+    a = torch.empty(M, 256, dtype=torch.bfloat16, device=DEV)
+    b = torch.empty_like(a)
+    G.skinny_fp8(x, codes, cs, a, G.SK_STORE, cus=32, splits=1)
+    G.skinny(x, w, b, G.SK_STORE, cus=32, splits=1)
+    assert torch.equal(a, b)
+    ref = x.float() @ w.float().t()
+    err = (b.float() - ref).abs().max().item()
+    print(f"M={M}: err {err:.4g} of max {ref.abs().max().item():.4g}")
+    assert err <= 0.01 * ref.abs().max().item() + 1e-3
+
+
 @pytest.mark.parametrize("steps", [1, 2, 3, 4, 5, 6])
 def test_skinny_fp8_pipeline_steps(steps):
     """One 128-column block, 5 rows, K of 1 .. 6 pipeline steps (128 deep):

@@ -31,6 +31,9 @@ def main() -> int:
     ap.add_argument("--micro-gemm", default="hip", choices=["hip", "rocblas"])
     ap.add_argument("--micro-weights", default="bf16", choices=["bf16", "fp8"],
                     help="layer weights of the micro-forwards (fp8: the W8A16 copy, ops.gemm.skinny_fp8)")
+    ap.add_argument("--fp8-tile", default="plan", choices=["plan", "never"],
+                    help="fp8: the FP8-weight tile kernel from the rows ops.gemm.fp8_plan says (plan), or "
+                         "thresholds above 1,024 rows = skinny_fp8 alone, the path before the tile kernel (never)")
     ap.add_argument("--budget", type=int, default=4096)
     ap.add_argument("--slots", type=int, default=1536)
     ap.add_argument("--blas", default="", choices=["", "lt", "rocblas"],
@@ -48,6 +51,11 @@ def main() -> int:
 
     from llm_message_queue_amd.backend.engine import BackendEngine, BackendHung, Request
     from llm_message_queue_amd.models.llama_stub import LlamaConfig
+    if a.fp8_tile == "never":
+        from llm_message_queue_amd.ops import gemm as G
+        for table in (G.FP8_TILE_MIN_M_SMALL, G.FP8_TILE_MIN_M_CHIP):
+            for k in table:
+                table[k] = G.SKINNY_CHUNKED_MAX_M + 1
     if a.blas:
         torch.backends.cuda.preferred_blas_library("cublaslt" if a.blas == "lt" else "cublas")
     dev = torch.device("cuda", 0)
@@ -114,7 +122,7 @@ def main() -> int:
                                   "rt_p99_ms": round(float(np.percentile(la, 99)), 1),
                                   "tok_s": round(eng.total_tokens / (t_rep - t0), 0),
                                   "graph_steps": eng.micro_graph_steps, "micro_weights": a.micro_weights,
-                                  "weight_gib": round(eng.weight_bytes / 2 ** 30, 2)}), flush=True)
+                                  "fp8_tile": a.fp8_tile, "weight_gib": round(eng.weight_bytes / 2 ** 30, 2)}), flush=True)
         eng.finish(block=True)
         eng.close()
         if a.stream == "partition":

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "classify_kernels.h"
+#include "gemm_fp8w_kernels.h"
 #include "gemm_kernels.h"
 #include "kv_migrate_kernels.h"
 #include "llama_kernels.h"
@@ -288,6 +289,44 @@ static void gemm_bf16(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K
     case GM_EPI_RESID_LDS: launch_gemm<GM_EPI_RESID_LDS>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
     case GM_EPI_RESID_PRE: launch_gemm<GM_EPI_RESID_PRE>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
     default: throw std::invalid_argument("gemm: unknown epilogue");
+  }
+  check_launch();
+}
+
+// The tile GEMM over FP8 weights (gemm_fp8w_kernels.h): wq [N][K] uint8 e4m3
+// codes, cs [N] fp32 column scales; epi 0 = store, 2 = SwiGLU, 6 = residual
+// add (LDS epilogue); rs and the split arguments as gemm_bf16's.
+template <int EPI>
+static void launch_gemm_fp8w(uintptr_t a, uintptr_t wq, uintptr_t cs, uintptr_t c, int M, int N, int K,
+                             uintptr_t stream, int group_m, const float* rs, const GmSplit& sp) {
+  static bool attr = false;
+  const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
+  const int nb = sp.ws ? sp.full + 2 * (tiles - sp.full) : tiles;
+  if (!attr) {
+    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_fp8w_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  GM_LDS_BYTES));
+    attr = true;
+  }
+  hipLaunchKernelGGL((gemm_fp8w_kernel<EPI>), dim3(nb), dim3(GM_THREADS), GM_LDS_BYTES, S(stream),
+                     P<const uint16_t>(a), P<const uint8_t>(wq), P<const float>(cs), P<uint16_t>(c), M, N, K,
+                     group_m, rs, sp);
+}
+
+static void gemm_fp8w(uintptr_t a, uintptr_t wq, uintptr_t cs, uintptr_t c, int M, int N, int K, int epi,
+                      uintptr_t stream, int group_m, uintptr_t rs, int split_full, uintptr_t split_ws,
+                      uintptr_t split_cnt) {
+  const bool resid = epi == GM_EPI_RESID_LDS;
+  check_gemm_operands("gemm_fp8w", a, wq, c, M, N, K, group_m, resid);
+  require(c != 0, "gemm_fp8w: null output");
+  require(cs != 0 && cs % 16 == 0, "gemm_fp8w: column scales must be non-null and 16-byte aligned");
+  require(epi == GM_EPI_STORE || epi == GM_EPI_SWIGLU || epi == GM_EPI_RESID_LDS, "gemm_fp8w: unknown epilogue");
+  const float* rsp = rs ? P<const float>(rs) : nullptr;
+  const GmSplit sp = make_split("gemm_fp8w", M, N, K, split_full, split_ws, split_cnt);
+  require(!resid || !rsp, "gemm_fp8w: the residual epilogue takes no row scale");
+  switch (epi) {
+    case GM_EPI_STORE: launch_gemm_fp8w<GM_EPI_STORE>(a, wq, cs, c, M, N, K, stream, group_m, rsp, sp); break;
+    case GM_EPI_SWIGLU: launch_gemm_fp8w<GM_EPI_SWIGLU>(a, wq, cs, c, M, N, K, stream, group_m, rsp, sp); break;
+    default: launch_gemm_fp8w<GM_EPI_RESID_LDS>(a, wq, cs, c, M, N, K, stream, group_m, rsp, sp); break;
   }
   check_launch();
 }
@@ -707,6 +746,9 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("K"), py::arg("epi"), py::arg("rs"), py::arg("ws"), py::arg("S"), py::arg("stream"));
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8, py::arg("a"), py::arg("wq"), py::arg("cs"), py::arg("c"), py::arg("M"),
         py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("rs"), py::arg("ws"), py::arg("S"), py::arg("stream"));
+  m.def("gemm_fp8w", &gemm_fp8w, py::arg("a"), py::arg("wq"), py::arg("cs"), py::arg("c"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("stream"), py::arg("group_m") = (int)GM_GROUP_M,
+        py::arg("rs") = 0, py::arg("split_full") = 0, py::arg("split_ws") = 0, py::arg("split_cnt") = 0);
   m.def("quant_rows_e4m3", &quant_rows_e4m3);
   m.def("fp8_decode", &fp8_decode);
   m.def("stream_with_cu_mask", &stream_with_cu_mask);

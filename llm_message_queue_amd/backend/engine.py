@@ -238,7 +238,7 @@ class BackendEngine:
         self.micro_gemm = micro_gemm
         # the layer weights the micro-forwards read: "bf16" = the serving
         # pool's, "fp8" = an e4m3 copy with one scale a row (W8A16: half the
-        # bytes a micro-forward streams; ops.quant, ops.gemm.skinny_fp8).  A
+        # bytes a micro-forward streams; ops.quant, ops.gemm.skinny_fp8 / gemm_fp8).  A
         # request of the micro pool then sees the quantised model in all its
         # forwards, eager or graph-replayed, so its tokens differ from the
         # serving pool's (``Request.micro`` tells which pool served it).

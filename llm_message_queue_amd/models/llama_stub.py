@@ -299,8 +299,10 @@ class LlamaStub:
         computation.  Returns [len(rows), d] then, else [T, d].
 
         ``quant``: the four GEMMs of every layer read the layer's FP8 weights
-        -- with the HIP ops on ``ops.gemm.skinny_fp8`` at any row count up to
-        ``SKINNY_CHUNKED_MAX_M`` (never a bf16 kernel: a request sees one
+        -- with the HIP ops on ``ops.gemm.skinny_fp8`` or, from the row
+        counts of ``ops.gemm.fp8_plan`` on, the FP8-weight tile kernel
+        (``gemm_fp8`` / ``gemm_swiglu_fp8`` / ``gemm_residual_fp8``), up to
+        ``SKINNY_CHUNKED_MAX_M`` rows (never a bf16 kernel: a request sees one
         model in all its forwards), with the reference ops on the decoded
         weights (``ops.quant.dequantize``), which is the same arithmetic."""
         cfg, ops = self.cfg, self.ops
@@ -342,7 +344,9 @@ class LlamaStub:
             if quant or skinny:
                 qkv = torch.empty((T, L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
                 rs = ops.row_rms(res, cfg.eps)
-                if quant:
+                if quant and G.fp8_plan(T, "qkv", small) == "tile":
+                    G.gemm_fp8(res, *L["fp8"]["wqkv"], out=qkv, row_scale=rs, split_cus=sk_cus)
+                elif quant:
                     G.skinny_fp8(res, *L["fp8"]["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=sk_cus or 32)
                 else:
                     G.skinny(res, L["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=sk_cus)
@@ -393,16 +397,29 @@ class LlamaStub:
         ``small_cus``: a micro-forward's small step on its CU partition --
         the hand-written kernels at any row count, split-K (``forward``).
         ``quant``: o, gate/up and down on the FP8 weights in ``L["fp8"]``
-        (``skinny_fp8``, any row count it takes)."""
+        (``skinny_fp8`` or the FP8-weight tile kernel, as ``ops.gemm.fp8_plan``
+        says for this block's row count)."""
         cfg, ops = self.cfg, self.ops
         M = res.shape[0]
         small = small_cus > 0
         if quant:
             cus = small_cus or self._cus or 32
-            G.skinny_fp8(a, *L["fp8"]["wo"], res, G.SK_RESID, cus=cus)
+            split = small_cus or self._cus               # the tile kernel's split-K plan: as the bf16 branch
+
+            def into_res_fp8(x, name, gemm):             # res += x · W[name]ᵀ on the kernel fp8_plan names
+                if G.fp8_plan(M, gemm, small) == "tile":
+                    G.gemm_residual_fp8(x, *L["fp8"][name], res, split_cus=split)
+                else:
+                    G.skinny_fp8(x, *L["fp8"][name], res, G.SK_RESID, cus=cus)
+
+            into_res_fp8(a, "wo", "o")
             act = torch.empty((M, L["w_gu"].shape[0] // 2), dtype=res.dtype, device=res.device)
-            G.skinny_fp8(res, *L["fp8"]["w_gu"], act, G.SK_SWIGLU, row_scale=ops.row_rms(res, cfg.eps), cus=cus)
-            G.skinny_fp8(act, *L["fp8"]["w_down"], res, G.SK_RESID, cus=cus)
+            rs = ops.row_rms(res, cfg.eps)
+            if G.fp8_plan(M, "gu", small) == "tile":
+                G.gemm_swiglu_fp8(res, *L["fp8"]["w_gu"], out=act, row_scale=rs, split_cus=split)
+            else:
+                G.skinny_fp8(res, *L["fp8"]["w_gu"], act, G.SK_SWIGLU, row_scale=rs, cus=cus)
+            into_res_fp8(act, "w_down", "down")
             return None
         # library-free (``library_gemm`` False): the hand-written kernels at
         # every row count, split-K where whole tiles leave CUs idle

@@ -13,6 +13,9 @@ three take ``row_scale`` (the folded RMSNorm).  A step too small to fill the
 CUs runs split-K (:func:`split_plan`, :func:`split_all`) or, below
 ``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`; :func:`skinny_fp8`
 over FP8 weight codes, :func:`quantize_rows` to make them -- ``ops.quant``).
+``gemm_fp8`` / ``gemm_swiglu_fp8`` / ``gemm_residual_fp8`` are the tile kernel
+over the same FP8 codes (``gemm_fp8w_kernels.h``); :func:`fp8_plan` says which
+of the two FP8 kernels a quant forward's GEMM takes.
 
 CPU / reference path: :func:`swiglu_reference` (fp32 math of the same op).
 """
@@ -172,18 +175,24 @@ def _launch(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, group
     if not supported(M, N, K):
         raise ValueError(f"gemm: unsupported shape M={M} N={N} K={K}")
     stream = torch.cuda.current_stream(x.device).cuda_stream
+    k.gemm_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, epi, stream, group_m,
+                _row_scale_ptr(row_scale, M), *_split_args(x.device, stream, M, N, K, split_cus))
+    return out
+
+
+def _split_args(device, stream: int, M: int, N: int, K: int, split_cus: int):
+    """The launchers' ``(split_full, workspace, counters)`` for ``split_cus``
+    CUs: every tile split (:func:`split_all`), else only a half-empty last
+    wave (:func:`split_plan`), else (0, 0, 0) = whole tiles."""
     f = None
-    if split_cus:                                      # every tile split, else only a half-empty last wave
+    if split_cus:
         f = split_all(M, N, K, split_cus)
         f = split_plan(M, N, K, split_cus) if f is None else f
-    ws = cnt = 0
-    if f is not None:
-        n_split = _tiles(M, N) - f
-        w_t, c_t = _split_workspace(x.device, stream, n_split, max(split_cus, 2 * n_split))
-        ws, cnt = w_t.data_ptr(), c_t.data_ptr()
-    k.gemm_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, epi, stream, group_m,
-                _row_scale_ptr(row_scale, M), f or 0, ws, cnt)
-    return out
+    if f is None:
+        return 0, 0, 0
+    n_split = _tiles(M, N) - f
+    w_t, c_t = _split_workspace(device, stream, n_split, max(split_cus, 2 * n_split))
+    return f, w_t.data_ptr(), c_t.data_ptr()
 
 
 def gemm(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor = None, row_scale=None,
@@ -449,6 +458,100 @@ def skinny_fp8(x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, ou
     _native.require_hipops().skinny_gemm_fp8(x.data_ptr(), codes.data_ptr(), col_scale.data_ptr(), out.data_ptr(),
                                              *args)
     return out
+
+
+# ---------------------------------------------------------------------- FP8-weight 256x256 tiles
+# Rows from which a quant forward's GEMM leaves the skinny kernel for the
+# FP8-weight tile kernel (csrc/kernels/gemm_fp8w_kernels.h), by GEMM of the
+# layer: on a micro-forward's CU partition (SMALL) and on the whole chip.
+# Every value is >= 65: the graph buckets stop at 64 rows, so decode-sized
+# micro-forwards and captured graphs keep the skinny kernel.  A value above
+# SKINNY_CHUNKED_MAX_M means never.  Each is the smallest measured M from
+# which the tile kernel beats skinny_fp8 by more than skinny_fp8's spread at
+# every larger M (profiles/fp8_tile_gemm_ab.jsonl, rows of that GEMM and
+# place; profiles/fp8_tile.md section 1): on 64 CUs qkv 0.96x at 128 and 1.51x at 192,
+# o 0.97x at 256 and 1.46x at 384, gate/up 1.008x at 65 already (spread
+# 0.4 %), down 0.66x at 128 and 1.11x at 192; on the chip the skinny kernel's
+# chunks spread over 256 CUs and hold out longer: qkv 0.76x at 256 and 1.016x
+# at 384, gate/up 0.96x at 65 and 1.09x at 96, o and down only at 1,024 rows
+# (1.05x, 1.27x; 0.71x, 0.74x at 512).
+FP8_GEMMS = ("qkv", "o", "gu", "down")
+FP8_TILE_MIN_M_SMALL = {"qkv": 192, "o": 384, "gu": 65, "down": 192}
+FP8_TILE_MIN_M_CHIP = {"qkv": 384, "o": 1024, "gu": 96, "down": 1024}
+
+
+def fp8_plan(M: int, gemm: str, small: bool) -> str:
+    """Which FP8 kernel GEMM ``gemm`` ("qkv", "o", "gu", "down") of a quant
+    forward takes at ``M`` rows: "skinny" or "tile".  ``small``: on a
+    micro-forward's CU partition.  Never "tile" at M <= SKINNY_MAX_M (the
+    graph buckets) or above SKINNY_CHUNKED_MAX_M (no quant forward is that
+    large)."""
+    table = FP8_TILE_MIN_M_SMALL if small else FP8_TILE_MIN_M_CHIP
+    if gemm not in table:
+        raise ValueError(f"fp8_plan: unknown GEMM {gemm!r}")
+    return "tile" if max(table[gemm], SKINNY_MAX_M + 1) <= M <= SKINNY_CHUNKED_MAX_M else "skinny"
+
+
+def _launch_fp8(fn: str, x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, out: torch.Tensor,
+                epi: int, row_scale=None, split_cus: int = 0):
+    """What the FP8-weight tile wrappers share: the checks of ``codes`` /
+    ``col_scale`` (as :func:`skinny_fp8`), the shape, the split-K plan and its
+    workspace (as :func:`_launch`: the same "split" scratch entry)."""
+    _check(x, "x")
+    _check(out, "out")
+    if codes.dtype != torch.uint8:
+        raise TypeError(f"{fn}: codes must be uint8, got {codes.dtype}")
+    if codes.dim() != 2 or not codes.is_contiguous() or codes.data_ptr() % 16:
+        raise ValueError(f"{fn}: codes must be contiguous 16-byte-aligned uint8 [N][K]")
+    N = codes.shape[0]
+    if col_scale.dtype != torch.float32 or tuple(col_scale.shape) != (N,) or not col_scale.is_contiguous() \
+            or col_scale.data_ptr() % 16:
+        raise ValueError(f"{fn}: col_scale must be contiguous 16-byte-aligned float32 [N]")
+    if codes.device != x.device or col_scale.device != x.device or out.device != x.device:
+        raise ValueError(f"{fn}: codes / col_scale / out must be on x's device")
+    if x.dim() != 2 or codes.shape[1] != x.shape[1]:
+        raise ValueError(f"{fn}: inner dimensions differ")
+    M, K = x.shape
+    if not supported(M, N, K):
+        raise ValueError(f"{fn}: unsupported shape M={M} N={N} K={K}")
+    want = (M, N // 2) if epi == EPI_SWIGLU else (M, N)
+    if tuple(out.shape) != want:
+        raise ValueError(f"{fn}: out shape {tuple(out.shape)} != {want}")
+    rs = _row_scale_ptr(row_scale, M)
+    k = _native.require_hipops()
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    k.gemm_fp8w(x.data_ptr(), codes.data_ptr(), col_scale.data_ptr(), out.data_ptr(), M, N, K, epi, stream, 8,
+                rs, *_split_args(x.device, stream, M, N, K, split_cus))
+    return out
+
+
+def gemm_fp8(x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, out: torch.Tensor = None,
+             row_scale=None, split_cus: int = 0) -> torch.Tensor:
+    """:func:`gemm` over FP8 weights (W8A16, ``ops.quant``): ``codes`` uint8
+    [N][K] e4m3fn and ``col_scale`` float32 [N], the tensors of
+    :func:`skinny_fp8`; ``out = (x . codesᵀ) * col_scale[n] * row_scale[m]``
+    on the 256x256-tile kernel, the codes decoded to bf16 in registers.  With
+    power-of-two scales bit-equal to :func:`gemm` over the decoded weights."""
+    y = out if out is not None else torch.empty((x.shape[0], codes.shape[0]), dtype=x.dtype, device=x.device)
+    return _launch_fp8("gemm_fp8", x, codes, col_scale, y, EPI_STORE, row_scale, split_cus)
+
+
+def gemm_swiglu_fp8(x: torch.Tensor, codes_perm: torch.Tensor, col_scale_perm: torch.Tensor,
+                    out: torch.Tensor = None, row_scale=None, split_cus: int = 0) -> torch.Tensor:
+    """:func:`gemm_swiglu` over FP8 weights: ``codes_perm`` / ``col_scale_perm``
+    follow the :func:`swiglu_permute`-d row order (the gate and the up row of
+    a feature carry their own scales) -> [M][F] bf16."""
+    y = out if out is not None else torch.empty((x.shape[0], codes_perm.shape[0] // 2), dtype=x.dtype,
+                                                device=x.device)
+    return _launch_fp8("gemm_swiglu_fp8", x, codes_perm, col_scale_perm, y, EPI_SWIGLU, row_scale, split_cus)
+
+
+def gemm_residual_fp8(x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, res: torch.Tensor,
+                      split_cus: int = 0) -> torch.Tensor:
+    """:func:`gemm_residual` over FP8 weights: ``res += (x . codesᵀ) *
+    col_scale[n]`` in place, one rounding of the fp32 sum (the LDS-DMA
+    residual epilogue).  Takes no row scale, as :func:`gemm_residual`."""
+    return _launch_fp8("gemm_residual_fp8", x, codes, col_scale, res, EPI_RESID_LDS, None, split_cus)
 
 
 def quantize_rows(w: torch.Tensor):

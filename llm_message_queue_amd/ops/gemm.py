@@ -245,8 +245,14 @@ def gemm_residual_rms(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, eps: 
     _check(res, "res")
     M, K = x.shape
     N = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != K:
+        raise ValueError("gemm_residual_rms: inner dimensions differ")
+    if not supported(M, N, K):
+        raise ValueError(f"gemm_residual_rms: unsupported shape M={M} N={N} K={K}")
     if res.shape != (M, N):
         raise ValueError("gemm_residual_rms: res shape mismatch")
+    if w.device != x.device or res.device != x.device:
+        raise ValueError("gemm_residual_rms: w / res must be on x's device")
     stream = torch.cuda.current_stream(x.device).cuda_stream
     tiles_m, tiles_n = (M + TILE_M - 1) // TILE_M, N // TILE_N
     part, ticket = _rms_workspace(x.device, stream, tiles_m, tiles_n)
@@ -351,8 +357,16 @@ def qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, pos: torch.Tensor, slot: torch
         raise ValueError("kv cache / rope table shape mismatch")
     if pos.numel() != T or slot.numel() != T:
         raise ValueError("pos / slot length must equal the token count")
+    if wqkv.dim() != 2 or wqkv.shape[1] != K:
+        raise ValueError("qkv_rope: inner dimensions differ")
     q = q_out if q_out is not None else torch.empty((T, Hq * 128), dtype=x.dtype, device=x.device)
     _check(q, "q_out")
+    if tuple(q.shape) != (T, Hq * 128):
+        raise ValueError(f"qkv_rope: q_out shape {tuple(q.shape)} != {(T, Hq * 128)}")
+    for t, n in ((wqkv, "wqkv"), (pos, "pos"), (slot, "slot"), (cos_t, "cos_t"), (sin_t, "sin_t"), (kc, "kc"),
+                 (vc, "vc"), (q, "q_out")):
+        if t.device != x.device:
+            raise ValueError(f"qkv_rope: {n} must be on x's device")
     k = _native.require_hipops()
     N = wqkv.shape[0]
     full, ws, cnt = 0, 0, 0

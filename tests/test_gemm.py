@@ -267,6 +267,7 @@ def test_qkv_rope_matches_linear_plus_rope_kv(T):
     untouched = torch.ones(S, max_ctx, dtype=torch.bool, device=DEV)
     untouched[slot.long(), pos.long()] = False
     assert (kc2.permute(0, 2, 1, 3)[untouched] == 0).all()
+    assert (vc2.permute(0, 2, 1, 3)[untouched] == 0).all()
 
 
 @pytest.mark.gpu

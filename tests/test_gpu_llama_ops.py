@@ -5,12 +5,12 @@ rows and sentinel-filled caches; the bounds come from the number formats
 import pytest
 import torch
 
+from kernel_checks import BF16_MIN_NORMAL, SENTINEL, _bf16, _rope_ref, sentinel, ulp_distance
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
 EPS = 1e-5
-SENTINEL = 0x5A5A
-BF16_MIN_NORMAL = 2.0 ** -126
 
 
 @pytest.fixture(scope="module")
@@ -19,29 +19,8 @@ def hip():
     return HipOps()
 
 
-def _bf16(x):
-    return x.to(torch.bfloat16)
-
-
-def _ordered(t):
-    """bf16 bit patterns as integers in value order (ulp distances)."""
-    i = t.contiguous().view(torch.int16).to(torch.int32)
-    return torch.where(i < 0, -(i & 0x7FFF), i)
-
-
-def ulp_distance(y, ref64):
-    """Largest distance, in bf16 steps, between y and the correctly rounded reference."""
-    return int((_ordered(y.cpu()) - _ordered(_bf16(ref64.float()))).abs().max())
-
-
-def _bf16_ulp(r):
-    """Spacing of bf16 at |r| (float64 tensor)."""
-    e = torch.floor(torch.log2(r.abs().clamp(min=BF16_MIN_NORMAL)))
-    return torch.exp2(e - 7)
-
-
 def _sentinel(shape):
-    return torch.full(shape, SENTINEL, dtype=torch.int16, device=DEV).view(torch.bfloat16)
+    return sentinel(shape, DEV)
 
 
 # ----------------------------------------------------------------------------- rmsnorm
@@ -155,17 +134,6 @@ def test_silu_mul_vs_fp64(hip, T, F, perm):
 # ----------------------------------------------------------------------------- rope_kv
 S, C = 3, 320
 TOKENS = [(2, 0), (0, 1), (1, C - 1), (0, 0), (2, C - 1), (1, 1), (0, 17)]          # (slot, pos), shuffled
-
-
-def _rope_ref(x64, cos64, sin64):
-    """x [T, H, 128], cos / sin [T, 64] -> rotate-half result, its bound
-    (1 bf16 ulp + the fp32 rounding of two products and a sum: an FMA or a
-    plain multiply-add both fit) in float64."""
-    a, b = x64[..., :64], x64[..., 64:]
-    c, s = cos64[:, None, :], sin64[:, None, :]
-    ref = torch.cat([a * c - b * s, b * c + a * s], dim=-1)
-    mag = torch.cat([(a * c).abs() + (b * s).abs(), (b * c).abs() + (a * s).abs()], dim=-1)
-    return ref, _bf16_ulp(ref) + 2.0 ** -22 * mag
 
 
 def _rope_case(Hq, Hkv, tokens, seed, n_slots=S, front=0, back=0):

@@ -1,15 +1,18 @@
 // Hand-written gfx950 bf16 GEMM of the backend model: C = A · Wᵀ with
 // A [M][K] and W [N][K] both K-contiguous (the layout F.linear feeds
-// hipBLASLt), fp32 accumulation on v_mfma_f32_16x16x32_bf16.  One kernel,
-// gemm_bf16_kernel<EPI>, with nine epilogues (host entry point in hipops.hip):
+// hipBLASLt), fp32 accumulation on v_mfma_f32_16x16x32_bf16.  One function,
+// gemm_tile<EPI, DIAG, FP8>, is the body of every kernel here:
+// gemm_bf16_kernel<EPI> with nine epilogues, and gemm_fp8w_kernel<EPI>, the
+// same tile over FP8 weights (W8A16; "The FP8 weight format" below) with
+// three of them (host entry points in hipops.hip):
 //
-//   GM_EPI_STORE      C[M][N] = A·Wᵀ (bf16)                           gemm_bf16
-//   GM_EPI_SWIGLU     H[M][N/2] = silu(A·Wgᵀ) * (A·Wuᵀ)               gemm_bf16
+//   GM_EPI_STORE      C[M][N] = A·Wᵀ (bf16)                           gemm_bf16, gemm_fp8w
+//   GM_EPI_SWIGLU     H[M][N/2] = silu(A·Wgᵀ) * (A·Wuᵀ)               gemm_bf16, gemm_fp8w
 //   GM_EPI_ROPE       qkv projection + RoPE + K/V cache write         gemm_qkv_rope
 //   GM_EPI_ARGMAX     LM head + greedy argmax, no logits tensor       gemm_argmax
 //   GM_EPI_SAMPLE     LM head + per-row temperature sampling          gemm_sample
 //   GM_EPI_RESID      C[M][N] += A·Wᵀ, residual through registers     gemm_bf16 (A/B)
-//   GM_EPI_RESID_LDS  ... residual tile staged into LDS by DMA        gemm_bf16 (default)
+//   GM_EPI_RESID_LDS  ... residual tile staged into LDS by DMA        gemm_bf16 (default), gemm_fp8w
 //   GM_EPI_RESID_PRE  ... its first quarter fetched at kernel start   gemm_bf16 (A/B)
 //   GM_EPI_RESID_RMS  GM_EPI_RESID_LDS + the RMSNorm row scales       gemm_residual_rms
 //
@@ -53,11 +56,50 @@
 //     running tiles share A and W panels in that XCD's L2.
 //   * M need not be a multiple of 256: A rows are clamped on load, rows >= M
 //     are not stored.  K % 128 == 0 and N % 256 == 0 are checked by the host.
+//
+// The FP8 weight format (gemm_tile<EPI, GM_DIAG_NONE, true>, EPI in STORE /
+// SWIGLU / RESID_LDS): C (+)= (A · decode(Wq)ᵀ) * cs[n] * rs[m] with Wq [N][K]
+// uint8 e4m3fn codes (K-contiguous, the tensor the skinny FP8 kernel reads) and
+// one fp32 scale a weight row, cs [N] (ops/quant.py holds the contract).  For
+// the micro-forwards that carry prefill (more than 64 rows), where the skinny
+// kernel's 128-row chunks re-read and re-decode their weights a chunk.  Every
+// k enters the MFMA step (K-tile, kk) and operand slot (lane fq, element) it
+// enters in the bf16 form, so with power-of-two scales the result is bit-equal
+// to gemm_bf16_kernel over the decoded weights.  Everything above holds; what
+// differs sits behind `if constexpr (FP8)` in gemm_tile:
+//   * A B half-tile is 128 columns x 64 codes = 8 KiB of 64-byte rows: ONE
+//     16-byte buffer_load ... lds a lane (wave w: rows 16w .. 16w + 15, four
+//     lanes a row).  LDS row lr holds column (lr / 32) * 64 + h * 32 + lr % 32
+//     of the tile, as the bf16 image.  Operand LDS: 2 x (2 x 16 + 2 x 8) =
+//     96 KiB; the launch still asks for 128 KiB, which the store and residual
+//     epilogues use (8 waves x 16 KiB).
+//   * Swizzle of the B image: the 16-byte chunk c of row r sits in slot
+//     c ^ ((r >> 2) & 3), applied to the per-lane SOURCE address and to the
+//     read address.  A B fragment is 8 bytes a lane (ds_read_b64: two 32-lane
+//     groups, bank = (addr / 4) % 64, i.e. addr % 256).  A group is 16 rows fr
+//     x two lanes fq (2g, 2g + 1) that read the two 8-byte halves of source
+//     chunk g + 2 kk: address % 256 = (fr & 3) * 64 + ((g + 2 kk) ^ (fr >> 2))
+//     * 16 + (fq & 1) * 8.  fr & 3 picks the 64-byte quarter, fr >> 2 (four
+//     values, xor with a constant is a bijection) the 16-byte slot in it,
+//     fq & 1 the half: 32 lanes, 32 distinct 8-byte bank pairs -- no conflict.
+//     (Unswizzled, rows r and r + 4 would share their banks: 4-way.)
+//   * The codes are decoded to bf16 in registers after the fragment read, right
+//     before the MFMAs that use them (sk_fp8x8_bf16: 4 VALU ops a fragment,
+//     16 a phase beside its 16 MFMAs); the raw fragments are 2 VGPRs each.
+//   * The counted waits follow the DMAs a half-tile (the table at kFlyA in
+//     gemm_tile).
+//   * The column scale multiplies the fp32 accumulators after the split-K
+//     join, before the row scale and any epilogue math: a lane owns columns
+//     tn * 256 + wc * 64 + nh * 32 + n * 16 + fr (under SwiGLU gate and up of
+//     a feature carry different scales; cs follows the permuted row order).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "fp8_decode.h"
 #include "sample_noise.h"
 
 namespace llmq {
@@ -97,14 +139,14 @@ enum {
   GM_DIAG_L2_PANELS = 6      // every block stages the panels of tile (0, 0): staging served from L2
 };
 
+// Epilogue side outputs.
 // GM_EPI_ARGMAX: the LM head's greedy sampling as the epilogue -- no [M][N]
 // logits tensor.  Each tile writes, per row, the max over its 256 columns and
 // the (global) column of its first occurrence into pv / pi [M][N / 256];
 // gemm_argmax_reduce_kernel picks the first maximum over the tiles (ties go
 // to the lower column, as torch.argmax does).  Values are the fp32
 // accumulators (not bf16-rounded logits).
-// Epilogue side outputs.  GM_EPI_ARGMAX: per-(row, column tile) max value /
-// index partials (pv, pi).  GM_EPI_RESID_RMS (GM_EPI_RESID_LDS plus): the
+// GM_EPI_RESID_RMS (GM_EPI_RESID_LDS plus): the
 // RMSNorm row scale of the updated residual rows, fused into the epilogue --
 // each block's per-row sums of squares of the bf16 values it stores (rpart
 // [tiles_m][tiles_n][256], written through to memory), and the last of a
@@ -203,7 +245,7 @@ __device__ __forceinline__ void gm_stage(__amdgpu_buffer_rsrc_t rs, uint32_t v0,
 }
 
 #define GM_LGKM(N) asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory")
-#define GM_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+#define GM_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")   // N: a constant expression
 #define GM_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define GM_BARRIER()                  \
   do {                                \
@@ -211,6 +253,20 @@ __device__ __forceinline__ void gm_stage(__amdgpu_buffer_rsrc_t rs, uint32_t v0,
     __builtin_amdgcn_s_barrier();     \
     GM_FENCE();                       \
   } while (0)
+
+// One 8-byte LDS read that stays a ds_read_b64 (the FP8 form's B fragments).
+// Left to the compiler, the n = 0 / n = 1 fragments (1 KiB apart) pair into
+// ds_read2st64_b64, which takes twice the LDS cycles and banks by 16-lane
+// groups modulo 32 (a 2-way conflict on this image).  The compiler does not
+// count this read in lgkmcnt: GM_PHASE_END waits lgkmcnt(0) and fences before
+// the first use.
+typedef __attribute__((ext_vector_type(2))) unsigned int gf_u32x2;
+template <int OFF>
+__device__ __forceinline__ gf_u32x2 gf_lds_read_b64(uint32_t addr) {
+  gf_u32x2 r;
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
+  return r;
+}
 
 // XCD-contiguous remap (bijective for any count): the dispatcher puts block
 // b of PER * count blocks on XCD b % 8; the XCDs take contiguous runs of the
@@ -334,12 +390,23 @@ __device__ __forceinline__ bool gm_split_join(uint8_t* __restrict__ smem, gm_acc
 // split-K join (gm_split_join), then one `if constexpr` branch per epilogue
 // family.  The main loop and the epilogues stay in this one function on
 // purpose: hoisting either into a function of its own changes the kernels'
-// register allocation (profiles/gemm_refactor.md).
-template <int EPI, int DIAG>
+// register allocation (profiles/gemm_refactor.md).  The weight format is a
+// parameter for the same reason: FP8 = true (W: uint8 codes, cs: their column
+// scales; the file header) differs in `if constexpr (FP8)` branches in place,
+// which leave the bf16 kernels' instructions what they were
+// (profiles/gemm_fp8w_merge.md).
+template <int EPI, int DIAG, bool FP8 = false>
 __device__ __forceinline__ void gemm_tile(
-    uint8_t* __restrict__ smem, const uint16_t* __restrict__ A, const uint16_t* __restrict__ W,
-    uint16_t* __restrict__ C, int M, int N, int K, int group_m, const float* __restrict__ rs, const GmRope& rp,
-    const GmSplit& sp, const GmSide& am, const int bid) {
+    uint8_t* __restrict__ smem, const uint16_t* __restrict__ A, const void* __restrict__ W,
+    const float* __restrict__ cs, uint16_t* __restrict__ C, int M, int N, int K, int group_m,
+    const float* __restrict__ rs, const GmRope& rp, const GmSplit& sp, const GmSide& am, const int bid) {
+  static_assert(!FP8 || (DIAG == GM_DIAG_NONE &&
+                         (EPI == GM_EPI_STORE || EPI == GM_EPI_SWIGLU || EPI == GM_EPI_RESID_LDS)),
+                "the FP8 form: STORE, SWIGLU and RESID_LDS, no diagnostics");
+  // a B half-tile (128 columns x BK): 16 KiB of bf16 or 8 KiB of codes; a K-tile buffer A0 A1 B0 B1
+  constexpr int kBHalf = 128 * GM_BK * (FP8 ? 1 : 2);
+  constexpr int kBuf = 2 * GM_HALF_BYTES + 2 * kBHalf;   // 64 KiB / 48 KiB
+  static_assert(2 * kBuf <= GM_LDS_BYTES, "operand buffers inside the launch's LDS");
   constexpr bool kStamp = DIAG == GM_DIAG_CLOCK || DIAG == GM_DIAG_CLOCK_NO_DMA;
   const int tiles_m = (M + GM_BM - 1) / GM_BM;
   const int tiles_n = N / GM_BN;
@@ -363,11 +430,15 @@ __device__ __forceinline__ void gemm_tile(
   const int wr = w >> 2, wc = w & 3;
 
   // ---- staging sources: half h, instruction i -> LDS local row lr = i*64 + w*8 + lane/8
+  // (FP8, B: half h, its one instruction -> LDS row w*16 + lane/4, slot lane%4)
   const int srow = w * 8 + (lane >> 3);            // 0..63
   const int schunk = (lane & 7) ^ ((srow >> 1) & 7);   // source chunk for LDS slot lane&7
+  const int brow = w * 16 + (lane >> 2);           // 0..127
+  const int bchunk = (lane & 3) ^ ((brow >> 2) & 3);   // source chunk for LDS slot lane&3
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, M * K * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, N * K * 2, 0x00020000);
-  uint32_t va[2][2], vb[2][2];                     // byte offsets (row, chunk) of K-tile 0
+  const __amdgpu_buffer_rsrc_t rsw =
+      __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, N * K * (FP8 ? 1 : 2), 0x00020000);
+  uint32_t va[2][2], vb[2][FP8 ? 1 : 2];           // byte offsets (row, chunk) of K-tile 0
   // (GM_DIAG_L2_PANELS: the panels of tile (0, 0), so nearly every staging read hits the XCD's L2)
   const int ltm = DIAG == GM_DIAG_L2_PANELS ? 0 : tm, ltn = DIAG == GM_DIAG_L2_PANELS ? 0 : tn;
 #pragma unroll
@@ -377,24 +448,36 @@ __device__ __forceinline__ void gemm_tile(
       int row = ltm * GM_BM + i * 128 + h * 64 + srow;
       row = row < M ? row : M - 1;
       va[h][i] = (uint32_t)row * (uint32_t)K * 2u + (uint32_t)schunk * 16u;
-      const int col = ltn * GM_BN + (2 * i + (w >> 2)) * 64 + h * 32 + (w & 3) * 8 + (lane >> 3);
-      vb[h][i] = (uint32_t)col * (uint32_t)K * 2u + (uint32_t)schunk * 16u;
+      if constexpr (!FP8) {
+        const int col = ltn * GM_BN + (2 * i + (w >> 2)) * 64 + h * 32 + (w & 3) * 8 + (lane >> 3);
+        vb[h][i] = (uint32_t)col * (uint32_t)K * 2u + (uint32_t)schunk * 16u;
+      }
+    }
+    if constexpr (FP8) {
+      const int col = ltn * GM_BN + (brow >> 5) * 64 + h * 32 + (brow & 31);
+      vb[h][0] = (uint32_t)col * (uint32_t)K + (uint32_t)bchunk * 16u;
     }
   }
   // LDS destination (wave-uniform) of instruction i inside a half-tile
   const uint32_t dst_i0 = (uint32_t)(w * 8) * 128u;
   const uint32_t dst_i1 = (uint32_t)(64 + w * 8) * 128u;
+  const uint32_t dst_b = (uint32_t)(w * 16) * 64u;   // FP8: of the one B instruction
 
-  // ---- fragment read offsets (bytes inside a half-tile), per k-step kk
+  // ---- fragment read offsets (bytes inside buffer 0), per k-step kk
+  const uint32_t sbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;   // LDS address
   const int fr = lane & 15, fq = lane >> 4;
-  uint32_t aoff[2][2], boff[2][2];                 // [buffer][kk]; buffer 1 = +64 KiB (beyond ds offset:)
+  uint32_t aoff[2][2], boff[2][2];                 // [buffer][kk]; buffer 1 = + kBuf (beyond ds offset:)
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    const int c = fq + 4 * kk;
+    const int c = fq + 4 * kk;                     // 8 k of the K-tile: 16 B of A and bf16 B, 8 B of codes
     aoff[0][kk] = (uint32_t)(wr * 64 + fr) * 128u + (uint32_t)((c ^ ((fr >> 1) & 7)) * 16);
-    boff[0][kk] = (uint32_t)(wc * 32 + fr) * 128u + (uint32_t)((c ^ ((fr >> 1) & 7)) * 16) + 2 * GM_HALF_BYTES;
-    aoff[1][kk] = aoff[0][kk] + GM_BUF_BYTES;
-    boff[1][kk] = boff[0][kk] + GM_BUF_BYTES;
+    if constexpr (FP8)
+      boff[0][kk] = (uint32_t)(2 * GM_HALF_BYTES) + (uint32_t)(wc * 32 + fr) * 64u +
+                    (uint32_t)(((c >> 1) ^ ((fr >> 2) & 3)) * 16 + (c & 1) * 8);
+    else
+      boff[0][kk] = (uint32_t)(wc * 32 + fr) * 128u + (uint32_t)((c ^ ((fr >> 1) & 7)) * 16) + 2 * GM_HALF_BYTES;
+    aoff[1][kk] = aoff[0][kk] + kBuf;
+    boff[1][kk] = boff[0][kk] + kBuf;
   }
 
   gm_acc_t acc;
@@ -408,21 +491,29 @@ __device__ __forceinline__ void gemm_tile(
         for (int d = 0; d < 2; ++d) acc[a][b][c][d] = gm_f32x4{0.f, 0.f, 0.f, 0.f};
 
   gm_bf16x8 af[4][2];                              // one m-half: [m][kk]
-  gm_bf16x8 bfr[2][2][2];                          // both n-halves: [nh][n][kk]
-  gm_bf16x8 b0y[2][2];                             // buffer 1's B0 fragments ([nh = 0] of bfr: buffer 0's)
+  using gm_bfrag = std::conditional_t<FP8, gf_u32x2, gm_bf16x8>;   // a B fragment: 8 codes or 8 bf16
+  gm_bfrag bfr[2][2][2];                           // both n-halves: [nh][n][kk]
+  gm_bfrag b0y[2][2];                              // buffer 1's B0 fragments ([nh = 0] of bfr: buffer 0's)
   // K-tiles of this block: all, or one half for a split tile (host: nt % 4 == 0)
   const int nt = khalf < 0 ? K / GM_BK : K / GM_BK / 2;
   const int kt0 = khalf > 0 ? nt : 0;
 
   // ---- the phase macros (every name they use is declared above)
+  // FP8: a B half is one 16-byte DMA a lane, its K-tile step GM_BK bytes
 #define GM_STAGE(BUF, HALF, KT)                                                               \
   do {                                                                                        \
-    const uint32_t _ko = (uint32_t)((KT) + kt0) * (GM_BK * 2);                                \
-    const uint32_t _b = (uint32_t)(BUF) * GM_BUF_BYTES + (uint32_t)(HALF) * GM_HALF_BYTES;   \
-    if constexpr ((HALF) < 2)                                                                 \
-      gm_stage(rsa, va[(HALF)][0], va[(HALF)][1], _ko, smem, _b + dst_i0, _b + dst_i1);       \
-    else                                                                                      \
-      gm_stage(rsw, vb[(HALF)-2][0], vb[(HALF)-2][1], _ko, smem, _b + dst_i0, _b + dst_i1);   \
+    if constexpr (FP8 && (HALF) >= 2) {                                                       \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(                                               \
+          rsw, (gm_lds_ptr)(smem + (uint32_t)(BUF) * kBuf + 2 * GM_HALF_BYTES + (uint32_t)((HALF)-2) * kBHalf + dst_b), \
+          16, vb[(HALF)-2][0], (uint32_t)((KT) + kt0) * GM_BK, 0, 0);                         \
+    } else {                                                                                  \
+      const uint32_t _ko = (uint32_t)((KT) + kt0) * (GM_BK * 2);                              \
+      const uint32_t _b = (uint32_t)(BUF) * kBuf + (uint32_t)(HALF) * GM_HALF_BYTES;          \
+      if constexpr ((HALF) < 2)                                                               \
+        gm_stage(rsa, va[(HALF)][0], va[(HALF)][1], _ko, smem, _b + dst_i0, _b + dst_i1);     \
+      else                                                                                    \
+        gm_stage(rsw, vb[(HALF)-2][0], vb[(HALF)-2][1], _ko, smem, _b + dst_i0, _b + dst_i1); \
+    }                                                                                         \
   } while (0)
 
 #define GM_READ_A(BUF, MH)                                                                     \
@@ -432,37 +523,60 @@ __device__ __forceinline__ void gemm_tile(
         af[m][kk] = *reinterpret_cast<const gm_bf16x8*>(smem + aoff[BUF][kk] + (MH) * GM_HALF_BYTES + m * 2048); \
   } while (0)
 
-#define GM_READ_B(BUF, NH)                                                                     \
+// the B fragments of n-half NH of buffer BUF (16 rows apart: 2 KiB, FP8 1 KiB) into DST[n][kk]
+#define GM_READ_B_INTO(BUF, NH, DST)                                                           \
   do {                                                                                         \
-    _Pragma("unroll") for (int n = 0; n < 2; ++n)                                              \
-      _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                         \
-        bfr[NH][n][kk] = *reinterpret_cast<const gm_bf16x8*>(smem + boff[BUF][kk] + (NH) * GM_HALF_BYTES + n * 2048); \
+    if constexpr (FP8) {                                                                       \
+      _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                       \
+        DST[0][kk] = gf_lds_read_b64<(NH) * kBHalf>(sbase + boff[BUF][kk]);                    \
+        DST[1][kk] = gf_lds_read_b64<(NH) * kBHalf + 1024>(sbase + boff[BUF][kk]);             \
+      }                                                                                        \
+    } else {                                                                                   \
+      _Pragma("unroll") for (int n = 0; n < 2; ++n)                                            \
+        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                       \
+          DST[n][kk] = *reinterpret_cast<const gm_bf16x8*>(smem + boff[BUF][kk] + (NH) * kBHalf + n * 2048); \
+    }                                                                                          \
   } while (0)
-
+#define GM_READ_B(BUF, NH) GM_READ_B_INTO(BUF, NH, bfr[NH])
 // B0 fragments into an explicit register set, MFMA with it
-#define GM_READ_B0_INTO(BUF, DST)                                                              \
-  do {                                                                                         \
-    _Pragma("unroll") for (int n = 0; n < 2; ++n)                                              \
-      _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                         \
-        DST[n][kk] = *reinterpret_cast<const gm_bf16x8*>(smem + boff[BUF][kk] + n * 2048);     \
-  } while (0)
+#define GM_READ_B0_INTO(BUF, DST) GM_READ_B_INTO(BUF, 0, DST)
 
+// (FP8: the codes of BREG decoded in front of the MFMAs that use them)
 #define GM_MFMA_WITH(MH, NH, BREG)                                                             \
   do {                                                                                         \
-    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                           \
+    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                         \
+      gm_bf16x8 _b[2];                                                                         \
+      _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                          \
+        if constexpr (FP8) _b[n] = sk_fp8x8_bf16(BREG[n][kk].x, BREG[n][kk].y);                \
+        else _b[n] = BREG[n][kk];                                                              \
+      }                                                                                        \
       _Pragma("unroll") for (int m = 0; m < 4; ++m)                                            \
         _Pragma("unroll") for (int n = 0; n < 2; ++n)                                          \
-          acc[MH][m][NH][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m][kk], BREG[n][kk],  \
+          acc[MH][m][NH][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m][kk], _b[n],        \
                                                                       acc[MH][m][NH][n], 0, 0, 0); \
+    }                                                                                          \
   } while (0)
 
-#define GM_PHASE_END(MH, NH, BREG) \
-  do {                             \
-    GM_BARRIER();                  \
-    GM_LGKM(0);                    \
-    GM_MFMA_WITH(MH, NH, BREG);    \
-    GM_BARRIER();                  \
+// (FP8: the fence keeps the decode behind the wait -- the asm fragment reads
+// are not in the compiler's lgkmcnt count, gf_lds_read_b64)
+#define GM_PHASE_END(MH, NH, BREG)   \
+  do {                               \
+    GM_BARRIER();                    \
+    GM_LGKM(0);                      \
+    if constexpr (FP8) GM_FENCE();   \
+    GM_MFMA_WITH(MH, NH, BREG);      \
+    GM_BARRIER();                    \
   } while (0)
+
+  // Counted waits.  A stage is kDmaA or kDmaB buffer_load ... lds a lane, and
+  // every phase must leave exactly the last three staged half-tiles in flight:
+  //     stage of the phase   in flight after it       s_waitcnt (bf16 / FP8)
+  //     A0 or A1             A, B, A                  kFlyA: vmcnt(6) / vmcnt(5)
+  //     B0 or B1             B, A, B                  kFlyB: vmcnt(6) / vmcnt(4)
+  //     prologue (7 halves)  B1, A0, B0 of buffer 1   kFlyB
+  //     drain phases 1-4     A1 B1 A0 / A1 B1 / A1 / -    6, 4, 2, 0 / 5, 3, 2, 0
+  constexpr int kDmaA = 2, kDmaB = FP8 ? 1 : 2;
+  constexpr int kFlyA = 2 * kDmaA + kDmaB, kFlyB = kDmaA + 2 * kDmaB;
 
   // ---- main loop: prologue
   // Wave priority: one static s_setprio 1 for wave row 1 (the
@@ -498,7 +612,7 @@ __device__ __forceinline__ void gemm_tile(
   GM_STAGE(1, GM_B0, 1);
   GM_STAGE(1, GM_A0, 1);
   GM_STAGE(1, GM_B1, 1);
-  GM_VMCNT(6);
+  GM_VMCNT(kFlyB);
   GM_BARRIER();
   GM_READ_B0_INTO(0, bfr[0]);
   if constexpr (DIAG >= GM_DIAG_SKIP_A2 && DIAG <= GM_DIAG_NO_DMA) {   // every fragment register defined
@@ -525,20 +639,20 @@ __device__ __forceinline__ void gemm_tile(
 #define GM_D_STAGE(B, H, K) do { if constexpr (kDma) GM_STAGE(B, H, K); } while (0)
   for (; t < nt - 2; t += 2) {
     {
-      GM_D_READ_A(kRdA, 0, 0); GM_D_STAGE(1, GM_A1, t + 1); GM_VMCNT(6); GM_PHASE_END(0, 0, bfr[0]);
-      GM_D_READ_B(0, 1); GM_D_STAGE(0, GM_B0, t + 2); GM_VMCNT(6); GM_PHASE_END(0, 1, bfr[1]);
-      GM_D_READ_A(kRdA2, 0, 1); GM_D_STAGE(0, GM_A0, t + 2); GM_VMCNT(6); GM_PHASE_END(1, 1, bfr[1]);
-      GM_D_READ_B0(1, b0y); GM_D_STAGE(0, GM_B1, t + 2); GM_VMCNT(6); GM_PHASE_END(1, 0, bfr[0]);
-      GM_D_READ_A(kRdA, 1, 0); GM_D_STAGE(0, GM_A1, t + 2); GM_VMCNT(6); GM_PHASE_END(0, 0, b0y);
-      GM_D_READ_B(1, 1); GM_D_STAGE(1, GM_B0, t + 3); GM_VMCNT(6); GM_PHASE_END(0, 1, bfr[1]);
-      GM_D_READ_A(kRdA2, 1, 1); GM_D_STAGE(1, GM_A0, t + 3); GM_VMCNT(6); GM_PHASE_END(1, 1, bfr[1]);
-      GM_D_READ_B0(0, bfr[0]); GM_D_STAGE(1, GM_B1, t + 3); GM_VMCNT(6); GM_PHASE_END(1, 0, b0y);
+      GM_D_READ_A(kRdA, 0, 0); GM_D_STAGE(1, GM_A1, t + 1); GM_VMCNT(kFlyA); GM_PHASE_END(0, 0, bfr[0]);
+      GM_D_READ_B(0, 1); GM_D_STAGE(0, GM_B0, t + 2); GM_VMCNT(kFlyB); GM_PHASE_END(0, 1, bfr[1]);
+      GM_D_READ_A(kRdA2, 0, 1); GM_D_STAGE(0, GM_A0, t + 2); GM_VMCNT(kFlyA); GM_PHASE_END(1, 1, bfr[1]);
+      GM_D_READ_B0(1, b0y); GM_D_STAGE(0, GM_B1, t + 2); GM_VMCNT(kFlyB); GM_PHASE_END(1, 0, bfr[0]);
+      GM_D_READ_A(kRdA, 1, 0); GM_D_STAGE(0, GM_A1, t + 2); GM_VMCNT(kFlyA); GM_PHASE_END(0, 0, b0y);
+      GM_D_READ_B(1, 1); GM_D_STAGE(1, GM_B0, t + 3); GM_VMCNT(kFlyB); GM_PHASE_END(0, 1, bfr[1]);
+      GM_D_READ_A(kRdA2, 1, 1); GM_D_STAGE(1, GM_A0, t + 3); GM_VMCNT(kFlyA); GM_PHASE_END(1, 1, bfr[1]);
+      GM_D_READ_B0(0, bfr[0]); GM_D_STAGE(1, GM_B1, t + 3); GM_VMCNT(kFlyB); GM_PHASE_END(1, 0, b0y);
     }
   }
   {                                              // ---- main loop: drain, the last two K-tiles
-      GM_READ_A(0, 0); GM_STAGE(1, GM_A1, t + 1); GM_VMCNT(6); GM_PHASE_END(0, 0, bfr[0]);
-      GM_READ_B(0, 1); GM_VMCNT(4); GM_PHASE_END(0, 1, bfr[1]);
-      GM_READ_A(0, 1); GM_VMCNT(2); GM_PHASE_END(1, 1, bfr[1]);
+      GM_READ_A(0, 0); GM_STAGE(1, GM_A1, t + 1); GM_VMCNT(kFlyA); GM_PHASE_END(0, 0, bfr[0]);
+      GM_READ_B(0, 1); GM_VMCNT(kDmaA + kDmaB); GM_PHASE_END(0, 1, bfr[1]);
+      GM_READ_A(0, 1); GM_VMCNT(kDmaA); GM_PHASE_END(1, 1, bfr[1]);
       GM_READ_B0_INTO(1, b0y); GM_VMCNT(0); GM_PHASE_END(1, 0, bfr[0]);
       GM_READ_A(1, 0); GM_PHASE_END(0, 0, b0y);
       GM_READ_B(1, 1); GM_PHASE_END(0, 1, bfr[1]);
@@ -555,11 +669,27 @@ __device__ __forceinline__ void gemm_tile(
 #undef GM_MFMA_WITH
 #undef GM_READ_B0_INTO
 #undef GM_READ_B
+#undef GM_READ_B_INTO
 #undef GM_READ_A
 #undef GM_STAGE
 
   // ---- split tile: the first K-half to finish hands its accumulators over
   if (khalf >= 0 && gm_split_join(smem, acc, sp, pid - full)) return;
+
+  // ---- FP8: the column scales of this lane's four columns, on the joined sums
+  if constexpr (FP8) {
+    const float* csp = cs + tn * GM_BN + wc * 64 + fr;
+#pragma unroll
+    for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        const float s = csp[nh * 32 + n * 16];
+#pragma unroll
+        for (int mh = 0; mh < 2; ++mh)
+#pragma unroll
+          for (int m = 0; m < 4; ++m) acc[mh][m][nh][n] *= s;
+      }
+  }
 
   // ---- epilogue through LDS (the staging buffers are free after the last barrier)
   const int row0 = tm * GM_BM + wr * 128;          // first output row of this wave
@@ -959,7 +1089,18 @@ __global__ __launch_bounds__(GM_THREADS) void gemm_bf16_kernel(
     int M, int N, int K, int group_m, const float* __restrict__ rs, const GmRope rp, const GmSplit sp,
     const GmSide am) {
   extern __shared__ __align__(16) uint8_t smem[];
-  gemm_tile<EPI, DIAG>(smem, A, W, C, M, N, K, group_m, rs, rp, sp, am, (int)blockIdx.x);
+  gemm_tile<EPI, DIAG>(smem, A, W, nullptr, C, M, N, K, group_m, rs, rp, sp, am, (int)blockIdx.x);
+}
+
+// The tile over FP8 weights (the file header): EPI in GM_EPI_STORE /
+// GM_EPI_SWIGLU / GM_EPI_RESID_LDS; Wq [N][K] e4m3 codes, cs [N] their scales
+template <int EPI>
+__global__ __launch_bounds__(GM_THREADS) void gemm_fp8w_kernel(
+    const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq, const float* __restrict__ cs,
+    uint16_t* __restrict__ C, int M, int N, int K, int group_m, const float* __restrict__ rs, const GmSplit sp) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  gemm_tile<EPI, GM_DIAG_NONE, true>(smem, A, Wq, cs, C, M, N, K, group_m, rs, GmRope{}, sp, GmSide{},
+                                     (int)blockIdx.x);
 }
 
 // out[row] = column of the first maximum over the tiles' partials (one wave per row)

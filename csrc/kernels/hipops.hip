@@ -16,7 +16,6 @@
 #include <vector>
 
 #include "classify_kernels.h"
-#include "gemm_fp8w_kernels.h"
 #include "gemm_kernels.h"
 #include "kv_migrate_kernels.h"
 #include "llama_kernels.h"
@@ -206,20 +205,29 @@ static void rmsnorm(uintptr_t x, uintptr_t res, uintptr_t w, uintptr_t y, int T,
 
 // ---------------------------------------------------------------------- 256 x 256 GEMM (gemm_kernels.h)
 // One block per tile, two per split tile (GmSplit); A [M][K], W [N][K], bf16.
-template <int EPI>
-static void launch_gemm(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, uintptr_t stream, int group_m,
-                        const float* rs = nullptr, const GmRope& rp = GmRope{},
+// FP8: w = e4m3 weight codes [N][K] bytes and cs = their fp32 column scales
+// [N] (gemm_fp8w_kernel<EPI>; EPI store, SwiGLU or residual-LDS).
+template <int EPI, bool FP8 = false>
+static void launch_gemm(uintptr_t a, uintptr_t w, uintptr_t cs, uintptr_t c, int M, int N, int K, uintptr_t stream,
+                        int group_m, const float* rs = nullptr, const GmRope& rp = GmRope{},
                         const GmSplit& sp = GmSplit{0, nullptr, nullptr}, const GmSide& am = GmSide{}) {
-  static bool attr = false;
+  static bool attr = false;                        // one per (EPI, FP8): one per kernel
   const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
   const int nb = sp.ws ? sp.full + 2 * (tiles - sp.full) : tiles;
+  const void* kern;
+  if constexpr (FP8) kern = (const void*)gemm_fp8w_kernel<EPI>;
+  else kern = (const void*)gemm_bf16_kernel<EPI>;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  gm_lds_bytes<EPI>()));
+    HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, gm_lds_bytes<EPI>()));
     attr = true;
   }
-  hipLaunchKernelGGL((gemm_bf16_kernel<EPI>), dim3(nb), dim3(GM_THREADS), gm_lds_bytes<EPI>(), S(stream),
-                     P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, group_m, rs, rp, sp, am);
+  if constexpr (FP8)
+    hipLaunchKernelGGL((gemm_fp8w_kernel<EPI>), dim3(nb), dim3(GM_THREADS), gm_lds_bytes<EPI>(), S(stream),
+                       P<const uint16_t>(a), P<const uint8_t>(w), P<const float>(cs), P<uint16_t>(c), M, N, K,
+                       group_m, rs, sp);
+  else
+    hipLaunchKernelGGL((gemm_bf16_kernel<EPI>), dim3(nb), dim3(GM_THREADS), gm_lds_bytes<EPI>(), S(stream),
+                       P<const uint16_t>(a), P<const uint16_t>(w), P<uint16_t>(c), M, N, K, group_m, rs, rp, sp, am);
 }
 
 // What every entry point of the kernel checks (``fn`` names it in the
@@ -261,7 +269,7 @@ static void gemm_residual_rms(uintptr_t a, uintptr_t w, uintptr_t c, int M, int 
   side.rticket = P<int>(ticket);
   side.rscale = P<float>(scale);
   side.reps = eps;
-  launch_gemm<GM_EPI_RESID_RMS>(a, w, c, M, N, K, stream, group_m, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr},
+  launch_gemm<GM_EPI_RESID_RMS>(a, w, 0, c, M, N, K, stream, group_m, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr},
                                 side);
   check_launch();
 }
@@ -274,61 +282,47 @@ static void gemm_residual_rms(uintptr_t a, uintptr_t w, uintptr_t c, int M, int 
 // (GmSplit; epilogues store / SwiGLU / residual-LDS): a step too small to
 // fill its CUs with whole tiles -- the realtime micro-forwards on their CU
 // partition, where o / down are 16 tiles for 32 CUs.
-static void gemm_bf16(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, int epi, uintptr_t stream,
-                      int group_m, uintptr_t rs, int split_full, uintptr_t split_ws, uintptr_t split_cnt) {
-  const bool resid = epi == GM_EPI_RESID || epi == GM_EPI_RESID_LDS || epi == GM_EPI_RESID_PRE;
-  check_gemm_operands("gemm", a, w, c, M, N, K, group_m, resid);
+// FP8: w = e4m3 codes [N][K] bytes, cs [N] their fp32 column scales; epi 0, 2
+// or 6 only.  ``fn`` names the entry point in every refusal.
+template <bool FP8>
+static void gemm_entry(const char* fn, uintptr_t a, uintptr_t w, uintptr_t cs, uintptr_t c, int M, int N, int K,
+                       int epi, uintptr_t stream, int group_m, uintptr_t rs, int split_full, uintptr_t split_ws,
+                       uintptr_t split_cnt) {
+  const bool split_epi = epi == GM_EPI_STORE || epi == GM_EPI_SWIGLU || epi == GM_EPI_RESID_LDS;
+  const bool resid = epi == GM_EPI_RESID_LDS || (!FP8 && (epi == GM_EPI_RESID || epi == GM_EPI_RESID_PRE));
+  check_gemm_operands(fn, a, w, c, M, N, K, group_m, resid);
+  if constexpr (FP8) {
+    require_in(fn, c != 0, "null output");
+    require_in(fn, cs != 0 && cs % 16 == 0, "column scales must be non-null and 16-byte aligned");
+    require_in(fn, split_epi, "unknown epilogue");
+  }
   const float* rsp = rs ? P<const float>(rs) : nullptr;
-  const GmSplit sp = make_split("gemm", M, N, K, split_full, split_ws, split_cnt);
-  require(!resid || !rsp, "gemm: the residual epilogues take no row scale");
-  require(!sp.ws || epi == GM_EPI_STORE || epi == GM_EPI_SWIGLU || epi == GM_EPI_RESID_LDS, "gemm: split-K epilogue");
+  const GmSplit sp = make_split(fn, M, N, K, split_full, split_ws, split_cnt);
+  require_in(fn, !resid || !rsp, "the residual epilogues take no row scale");
+  require_in(fn, !sp.ws || split_epi, "split-K epilogue");
+  auto launch = [&](auto e) {
+    launch_gemm<decltype(e)::value, FP8>(a, w, cs, c, M, N, K, stream, group_m, rsp, GmRope{}, sp);
+  };
   switch (epi) {
-    case GM_EPI_STORE: launch_gemm<GM_EPI_STORE>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
-    case GM_EPI_SWIGLU: launch_gemm<GM_EPI_SWIGLU>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
-    case GM_EPI_RESID: launch_gemm<GM_EPI_RESID>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
-    case GM_EPI_RESID_LDS: launch_gemm<GM_EPI_RESID_LDS>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
-    case GM_EPI_RESID_PRE: launch_gemm<GM_EPI_RESID_PRE>(a, w, c, M, N, K, stream, group_m, rsp, GmRope{}, sp); break;
-    default: throw std::invalid_argument("gemm: unknown epilogue");
+    case GM_EPI_STORE: launch(std::integral_constant<int, GM_EPI_STORE>{}); break;
+    case GM_EPI_SWIGLU: launch(std::integral_constant<int, GM_EPI_SWIGLU>{}); break;
+    case GM_EPI_RESID: if constexpr (!FP8) launch(std::integral_constant<int, GM_EPI_RESID>{}); break;
+    case GM_EPI_RESID_LDS: launch(std::integral_constant<int, GM_EPI_RESID_LDS>{}); break;
+    case GM_EPI_RESID_PRE: if constexpr (!FP8) launch(std::integral_constant<int, GM_EPI_RESID_PRE>{}); break;
+    default: throw std::invalid_argument(std::string(fn) + ": unknown epilogue");
   }
   check_launch();
 }
 
-// The tile GEMM over FP8 weights (gemm_fp8w_kernels.h): wq [N][K] uint8 e4m3
-// codes, cs [N] fp32 column scales; epi 0 = store, 2 = SwiGLU, 6 = residual
-// add (LDS epilogue); rs and the split arguments as gemm_bf16's.
-template <int EPI>
-static void launch_gemm_fp8w(uintptr_t a, uintptr_t wq, uintptr_t cs, uintptr_t c, int M, int N, int K,
-                             uintptr_t stream, int group_m, const float* rs, const GmSplit& sp) {
-  static bool attr = false;
-  const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GM_BN);
-  const int nb = sp.ws ? sp.full + 2 * (tiles - sp.full) : tiles;
-  if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_fp8w_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  GM_LDS_BYTES));
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_fp8w_kernel<EPI>), dim3(nb), dim3(GM_THREADS), GM_LDS_BYTES, S(stream),
-                     P<const uint16_t>(a), P<const uint8_t>(wq), P<const float>(cs), P<uint16_t>(c), M, N, K,
-                     group_m, rs, sp);
+static void gemm_bf16(uintptr_t a, uintptr_t w, uintptr_t c, int M, int N, int K, int epi, uintptr_t stream,
+                      int group_m, uintptr_t rs, int split_full, uintptr_t split_ws, uintptr_t split_cnt) {
+  gemm_entry<false>("gemm", a, w, 0, c, M, N, K, epi, stream, group_m, rs, split_full, split_ws, split_cnt);
 }
 
 static void gemm_fp8w(uintptr_t a, uintptr_t wq, uintptr_t cs, uintptr_t c, int M, int N, int K, int epi,
                       uintptr_t stream, int group_m, uintptr_t rs, int split_full, uintptr_t split_ws,
                       uintptr_t split_cnt) {
-  const bool resid = epi == GM_EPI_RESID_LDS;
-  check_gemm_operands("gemm_fp8w", a, wq, c, M, N, K, group_m, resid);
-  require(c != 0, "gemm_fp8w: null output");
-  require(cs != 0 && cs % 16 == 0, "gemm_fp8w: column scales must be non-null and 16-byte aligned");
-  require(epi == GM_EPI_STORE || epi == GM_EPI_SWIGLU || epi == GM_EPI_RESID_LDS, "gemm_fp8w: unknown epilogue");
-  const float* rsp = rs ? P<const float>(rs) : nullptr;
-  const GmSplit sp = make_split("gemm_fp8w", M, N, K, split_full, split_ws, split_cnt);
-  require(!resid || !rsp, "gemm_fp8w: the residual epilogue takes no row scale");
-  switch (epi) {
-    case GM_EPI_STORE: launch_gemm_fp8w<GM_EPI_STORE>(a, wq, cs, c, M, N, K, stream, group_m, rsp, sp); break;
-    case GM_EPI_SWIGLU: launch_gemm_fp8w<GM_EPI_SWIGLU>(a, wq, cs, c, M, N, K, stream, group_m, rsp, sp); break;
-    default: launch_gemm_fp8w<GM_EPI_RESID_LDS>(a, wq, cs, c, M, N, K, stream, group_m, rsp, sp); break;
-  }
-  check_launch();
+  gemm_entry<true>("gemm_fp8w", a, wq, cs, c, M, N, K, epi, stream, group_m, rs, split_full, split_ws, split_cnt);
 }
 
 // q = RoPE(x · Wq^T); K/V cache rows (slot, pos) = (RoPE(x · Wk^T), x · Wv^T):
@@ -346,7 +340,7 @@ static void gemm_qkv_rope(uintptr_t a, uintptr_t w, int M, int N, int K, uintptr
   require(max_ctx > 0 && n_slots > 0, "gemm_qkv_rope: bad cache shape");
   GmRope rp{P<const int32_t>(pos), P<const int32_t>(slot), P<const float>(cos_t), P<const float>(sin_t),
             P<uint16_t>(q), P<uint16_t>(kc), P<uint16_t>(vc), Hq, Hkv, max_ctx, n_slots};
-  launch_gemm<GM_EPI_ROPE>(a, w, 0, M, N, K, stream, group_m, rs ? P<const float>(rs) : nullptr, rp,
+  launch_gemm<GM_EPI_ROPE>(a, w, 0, 0, M, N, K, stream, group_m, rs ? P<const float>(rs) : nullptr, rp,
                            make_split("gemm_qkv_rope", M, N, K, split_full, split_ws, split_cnt));
   check_launch();
 }
@@ -358,7 +352,7 @@ static void launch_head(const char* fn, uintptr_t a, uintptr_t w, int M, int N, 
                         uintptr_t out, uintptr_t stream) {
   check_gemm_operands(fn, a, w, 0, M, N, K, GM_GROUP_M, false);
   require_in(fn, (uintptr_t)side.pv % 4 == 0 && (uintptr_t)side.pi % 4 == 0 && out % 4 == 0, "alignment");
-  launch_gemm<EPI>(a, w, 0, M, N, K, stream, GM_GROUP_M, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, side);
+  launch_gemm<EPI>(a, w, 0, 0, M, N, K, stream, GM_GROUP_M, nullptr, GmRope{}, GmSplit{0, nullptr, nullptr}, side);
   hipLaunchKernelGGL(gemm_argmax_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, S(stream), side.pv, side.pi, M,
                      N / GM_BN, P<int32_t>(out));
   check_launch();

@@ -46,11 +46,11 @@
 
 #include <type_traits>
 
+#include "fp8_decode.h"   // sk_fp8x8_bf16, sk_bf16x8, sk_u32x4
+
 namespace llmq {
 
-typedef __attribute__((ext_vector_type(8))) short sk_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float sk_f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int sk_u32x4;
 
 constexpr int SK_NB = 128;          // output columns per block
 constexpr int SK_KS = 128;          // K per pipeline step
@@ -63,20 +63,6 @@ enum { SK_EPI_STORE = 0, SK_EPI_RESID = 1, SK_EPI_SWIGLU = 2 };
 // chunks of a column block run on one XCD back to back (block b -> XCD b % 8:
 // chunk fastest within the XCD's share) and the repeats come from its L2.
 constexpr int SK_MAX_M = 1024;           // up to 8 chunks (o / down at mid-size steps)
-
-// fp8 (e4m3) -> bf16: bytes 2 HI, 2 HI + 1 of w -> two bf16 (low half first): the scaled pack
-// conversion with scale 1, one VALU op a pair.  (v_cvt_pk_f32_fp8 + packing
-// the two high halves measured 0-7 % slower per GEMM: profiles/skinny_fp8.md.)
-template <bool HI>
-__device__ __forceinline__ uint32_t sk_fp8x2_bf16(uint32_t w) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
-
-__device__ __forceinline__ sk_bf16x8 sk_fp8x8_bf16(uint32_t lo, uint32_t hi) {
-  const sk_u32x4 r = {sk_fp8x2_bf16<false>(lo), sk_fp8x2_bf16<true>(lo), sk_fp8x2_bf16<false>(hi),
-                      sk_fp8x2_bf16<true>(hi)};
-  return __builtin_bit_cast(sk_bf16x8, r);
-}
 
 // The weight format of skinny_partial_kernel: the element type, the register
 // stages ST of the ring and the 16-byte loads NV of a stage (a lane's run of a

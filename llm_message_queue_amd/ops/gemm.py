@@ -14,7 +14,7 @@ CUs runs split-K (:func:`split_plan`, :func:`split_all`) or, below
 ``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`; :func:`skinny_fp8`
 over FP8 weight codes, :func:`quantize_rows` to make them -- ``ops.quant``).
 ``gemm_fp8`` / ``gemm_swiglu_fp8`` / ``gemm_residual_fp8`` are the tile kernel
-over the same FP8 codes (``gemm_fp8w_kernels.h``); :func:`fp8_plan` says which
+over the same FP8 codes (``gemm_fp8w_kernel`` in ``gemm_kernels.h``); :func:`fp8_plan` says which
 of the two FP8 kernels a quant forward's GEMM takes.
 
 CPU / reference path: :func:`swiglu_reference` (fp32 math of the same op).
@@ -476,7 +476,7 @@ def skinny_fp8(x: torch.Tensor, codes: torch.Tensor, col_scale: torch.Tensor, ou
 
 # ---------------------------------------------------------------------- FP8-weight 256x256 tiles
 # Rows from which a quant forward's GEMM leaves the skinny kernel for the
-# FP8-weight tile kernel (csrc/kernels/gemm_fp8w_kernels.h), by GEMM of the
+# FP8-weight tile kernel (gemm_fp8w_kernel, csrc/kernels/gemm_kernels.h), by GEMM of the
 # layer: on a micro-forward's CU partition (SMALL) and on the whole chip.
 # Every value is >= 65: the graph buckets stop at 64 rows, so decode-sized
 # micro-forwards and captured graphs keep the skinny kernel.  A value above

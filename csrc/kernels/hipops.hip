@@ -19,6 +19,7 @@
 #include "gemm_kernels.h"
 #include "kv_migrate_kernels.h"
 #include "llama_kernels.h"
+#include "sample_truncate_kernels.h"
 #include "skinny_kernels.h"
 #include "summarise_kernels.h"
 #include "text_kernels.h"
@@ -391,6 +392,29 @@ static void sample_bits(uintptr_t keys, int n_keys, uint32_t n0, int count, uint
   check_launch();
 }
 
+// out[r] = the top-k / top-p truncated draw of row r of bf16 logits [R][ld] (columns < V):
+// sample_truncate_kernels.h holds the contract.  One block a row, grid-stride above ST_MAX_BLOCKS.
+static void sample_truncated(uintptr_t logits, int R, int V, int ld, uintptr_t inv_temp, uintptr_t keys,
+                             uintptr_t top_k, uintptr_t top_p, uintptr_t out, uintptr_t stream) {
+  const char* fn = "sample_truncated";
+  require_in(fn, R >= 0 && V > 0 && ld >= V && ld % 8 == 0, "needs R >= 0, 0 < V <= ld, ld % 8 == 0");
+  require_in(fn, logits != 0 && logits % 16 == 0, "logits must be 16-byte aligned");
+  require_in(fn, inv_temp != 0 && keys != 0 && top_k != 0 && top_p != 0 && out != 0, "null pointer");
+  require_in(fn, inv_temp % 4 == 0 && keys % 4 == 0 && top_k % 4 == 0 && top_p % 4 == 0 && out % 4 == 0,
+             "per-row arrays must be 4-byte aligned");
+  if (R == 0) return;
+  static bool attr = false;
+  if (!attr) {
+    HIP_CHECK(hipFuncSetAttribute((const void*)sample_truncated_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)ST_LDS_BYTES));
+    attr = true;
+  }
+  hipLaunchKernelGGL(sample_truncated_kernel, dim3(std::min(R, (int)ST_MAX_BLOCKS)), dim3(ST_THREADS), ST_LDS_BYTES,
+                     S(stream), P<const uint16_t>(logits), R, V, ld, P<const float>(inv_temp),
+                     P<const uint32_t>(keys), P<const int32_t>(top_k), P<const float>(top_p), P<int32_t>(out));
+  check_launch();
+}
+
 static void row_rms(uintptr_t x, uintptr_t r, int T, int D, float eps, uintptr_t stream) {
   require(T >= 0 && D > 0 && D % 512 == 0, "row_rms expects D % 512 == 0");
   require(x % 16 == 0 && r % 4 == 0, "row_rms: misaligned pointers");
@@ -720,6 +744,8 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("stream"));
   m.def("sample_bits", &sample_bits, py::arg("keys"), py::arg("n_keys"), py::arg("n0"), py::arg("count"),
         py::arg("out"), py::arg("stream"));
+  m.def("sample_truncated", &sample_truncated, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"),
+        py::arg("inv_temp"), py::arg("keys"), py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("stream"));
   m.def("row_rms", &row_rms);
   m.attr("GEMM_EPI_STORE") = (int)GM_EPI_STORE;
   m.attr("GEMM_EPI_SWIGLU") = (int)GM_EPI_SWIGLU;

@@ -77,9 +77,14 @@ class Request:
     dialog: bool = False
     # sampling: 0 = greedy, else tokens are drawn from softmax(logits /
     # temperature) with noise that is a pure function of (seed, index of the
-    # generated token, vocabulary column) -- ``ops.sampling``; no top-k / top-p
+    # generated token, vocabulary column) -- ``ops.sampling``.  With a
+    # temperature, ``top_k`` > 0 / ``top_p`` < 1 truncate the distribution
+    # first (``csrc/kernels/sample_truncate_kernels.h``); a greedy request
+    # ignores both
     temperature: float = 0.0
     seed: int = 0
+    top_k: int = 0
+    top_p: float = 1.0
 
 
 @dataclass
@@ -300,7 +305,10 @@ class BackendEngine:
         self.s_micro[slots:] = True
         self.s_temp = np.zeros(n_all, dtype=np.float32)     # sampling temperature (0: greedy)
         self.s_seed = np.zeros(n_all, dtype=np.uint64)      # sampling seed
+        self.s_topk = np.zeros(n_all, dtype=np.int32)       # top-k of a sampling slot (0: off)
+        self.s_topp = np.ones(n_all, dtype=np.float32)      # top-p of a sampling slot (1: off)
         self.sampled_steps = 0                              # forwards that ended in the sampling head
+        self.truncated_steps = 0                            # ... and drew a top-k / top-p row again (``truncated_head``)
         # host copy of every generated token id, per slot (written when the
         # step that sampled it is reaped; steps of one pool are reaped in
         # launch order, so a slot's next request never overwrites a row
@@ -338,8 +346,9 @@ class BackendEngine:
         # read it has finished: launch keeps <= max_inflight steps queued, so
         # step k reuses step k - ring's buffer only once that one was reaped)
         ring = max(2, self.max_inflight)
-        # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles)
-        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 2 * slots + 64 + 3 * row_scale_len(slots) + 4))
+        # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles,
+        #  and row index, top_k and top_p of its truncating rows)
+        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 5 * slots + 64 + 3 * row_scale_len(slots) + 4))
                       for _ in range(ring)]
         # sampled token ids copied back behind each forward (read at reap)
         self._out_pins = [self._alloc_pin(4 * self.n_all).view(torch.int32) for _ in range(ring)]
@@ -360,7 +369,7 @@ class BackendEngine:
             # so it never grows (a grown pinned buffer frees the old one
             # behind the copies still queued from it)
             self._pins_m = [self._alloc_pin(4 * (11 * self.micro_budget + 2 * self.micro_slots + 64
-                                                 + 3 * row_scale_len(self.micro_slots) + 4))
+                                                 + 3 * row_scale_len(self.micro_slots) + 3 * self.micro_slots + 4))
                             for _ in range(mr)]
             self._out_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32) for _ in range(mr)]
         # segment-tiled MFMA attention on the HIP path (per-token otherwise)
@@ -615,6 +624,11 @@ class BackendEngine:
                 self.s_seed[s] = int(r.seed) & 0xFFFFFFFFFFFFFFFF
             else:
                 self.s_temp[s] = 0.0
+            # truncation is active only on a slot that samples
+            on = self.s_temp[s] > 0
+            self.s_topk[s] = max(0, int(r.top_k)) if on else 0
+            tp = float(r.top_p)
+            self.s_topp[s] = tp if (on and 0.0 < tp < 1.0) else 1.0
             # prefill order key: realtime-lane tiers sort before everything else
             self.s_seq[s] = self._admit_seq - (1 << 48 if 0 <= r.tier < self.fast_tiers else 0)
             self._admit_seq += 1
@@ -1038,9 +1052,19 @@ class BackendEngine:
         # 16-byte aligned on the device (the epilogue's vector loads)
         o_smp = (o_til + 4 * NT + 3) & ~3 if sampling else o_til + 4 * NT
         Sp = row_scale_len(S) if sampling else 0
-        buf = np.empty(o_smp + 3 * Sp, dtype=np.int32)
+        # rows that also ask for top-k / top-p: their indices into the sampled
+        # rows, top_k and top_p (float32 bits) behind the keys, same copy
+        trows = np.flatnonzero((temp > 0) & ((self.s_topk[samp_slots] > 0) | (self.s_topp[samp_slots] < 1))) \
+            if sampling else ()
+        R = len(trows)
+        o_trn = o_smp + 3 * Sp
+        buf = np.empty(o_trn + 3 * R, dtype=np.int32)
+        if R:
+            buf[o_trn:o_trn + R] = trows
+            buf[o_trn + R:o_trn + 2 * R] = self.s_topk[samp_slots[trows]]
+            buf[o_trn + 2 * R:] = self.s_topp[samp_slots[trows]].view(np.int32)
         if sampling:
-            buf[o_til + 4 * NT:] = 0
+            buf[o_til + 4 * NT:o_trn] = 0
             buf[o_smp:o_smp + S] = inv_temperature(temp).view(np.int32)
             buf[o_smp + Sp:o_smp + Sp + 2 * S] = \
                 row_keys(self.s_seed[samp_slots], self.s_gen[samp_slots]).view(np.int32).reshape(-1)
@@ -1078,6 +1102,10 @@ class BackendEngine:
                 skw = {"inv_temp": d[o_smp:o_smp + Sp].view(torch.float32),
                        "keys": d[o_smp + Sp:o_smp + 3 * Sp].view(Sp, 2)}
                 self.sampled_steps += 1
+                if R:
+                    skw["trunc"] = (d[o_trn:o_trn + R].long(), d[o_trn + R:o_trn + 2 * R],
+                                    d[o_trn + 2 * R:o_trn + 3 * R].view(torch.float32))
+                    self.truncated_steps += 1
             ev0 = self._start_event()
             te = time.perf_counter_ns()
             fwd = self._micro_forward if micro else self.model.forward

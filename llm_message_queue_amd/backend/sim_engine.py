@@ -83,7 +83,7 @@ class SimEngine(BackendEngine):
         return (self.base_ms + self.tile_ms * -(-int(T) // 256)) / self.speed
 
     @staticmethod
-    def _forward(tok, pos, slot, samp, tiles=None, n_dec=0, inv_temp=None, keys=None):
+    def _forward(tok, pos, slot, samp, tiles=None, n_dec=0, inv_temp=None, keys=None, trunc=None):
         return torch.zeros(int(samp.shape[0]), dtype=torch.int32)
 
     def warm_shapes(self, sizes=None) -> int:

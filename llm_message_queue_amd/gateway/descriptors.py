@@ -29,9 +29,27 @@ K_HIST = 8
 DESC_HDR = 20       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/hi, gen, plen, flags, conv lo/hi,
 #                    dialog history length, decision - enq (us), processing timeout (ms),
 #                    sampling temperature (float32 bits), sampling seed lo/hi];
-#                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN
+#                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN | top_k << 10 | top_p permille << 20
 KV_MIGRATE = 1 << 8     # descriptor flag: hold the turn until its KV arrives from the home GPU
 DIALOG_TURN = 1 << 9    # descriptor flag: a conversation turn -- its generated ids go back with K_DONE
+# the sampling truncation of a request with a temperature, 10 bits each of the
+# flags column: top_k (0 = off, <= 1023) in bits 10-19, top_p in thousandths
+# in bits 20-29 (0 or 1000 = off).  A request without truncation leaves both
+# zero.  The engine's float is float32(permille / 1000) on every GPU.
+TOPK_SHIFT, TOPP_SHIFT, TRUNC_MASK = 10, 20, 0x3FF
+
+
+def pack_truncation(top_k: int, top_p: float) -> int:
+    """The flags-column bits of ``(top_k, top_p)`` (0: no truncation)."""
+    pm = int(round(float(top_p) * 1000.0))
+    pm = 0 if not 0 < pm < 1000 else pm
+    return (min(max(int(top_k), 0), TRUNC_MASK) << TOPK_SHIFT) | (pm << TOPP_SHIFT)
+
+
+def unpack_truncation(flags: int) -> tuple:
+    """``(top_k, top_p)`` of a flags column value."""
+    pm = (int(flags) >> TOPP_SHIFT) & TRUNC_MASK
+    return (int(flags) >> TOPK_SHIFT) & TRUNC_MASK, (pm / 1000.0 if 0 < pm < 1000 else 1.0)
 
 
 def conv_key(conversation_id: str) -> int:

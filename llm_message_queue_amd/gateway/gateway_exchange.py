@@ -27,7 +27,8 @@ from ..backend.engine import Request
 from ..models.message import Message, MessageStatus
 from ..parallel import planner
 from .descriptors import (DESC_HDR, DIALOG_TURN, FAIL_UNTOUCHED, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE, K_FAIL,
-                          K_HIST, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, _get64, _put64, conv_key)
+                          K_HIST, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, _get64, _put64, conv_key, pack_truncation,
+                          unpack_truncation)
 
 HIST_LEN_BITS = 20      # descriptor col 14: dialog history length | (compressed-context length << 20)
 from .latency import P_PLAN_LOCAL, P_PLAN_REMOTE
@@ -365,7 +366,8 @@ class ExchangeMixin:
             small[k, 4] = min(0x7FFFFFFF, max(0, (m.popped_ns - m.enqueued_at) // 1000)) \
                 if (m.popped_ns and m.enqueued_at) else 0
             small[k, 5] = min(0x7FFFFFFF, self._timeout_ns(m) // 1_000_000)
-            temp[k], seed[k] = self._sampling(m)
+            temp[k], seed[k], top_k, top_p = self._sampling(m)
+            small[k, 2] |= pack_truncation(top_k, top_p)
         buf[:, 0] = K_DISPATCH
         _put64(buf, 1, v[:, 0])
         buf[:, 3] = origin
@@ -473,6 +475,7 @@ class ExchangeMixin:
                 rows[:, 16].tolist(), rows[:, 11].tolist())):
             self._next_req += 1
             hl, pl = hv & mask, hv >> HIST_LEN_BITS
+            top_k, top_p = unpack_truncation(fl)
             # the dialog context's LENGTH travels here (a resident turn only
             # needs it to check its KV is current); a turn that must replay
             # waits for the real tokens (K_HIST, next exchange), which replace
@@ -482,7 +485,7 @@ class ExchangeMixin:
                                history=np.zeros(hl, dtype=np.int32) if hl > 0 else None,
                                prefix=np.zeros(pl, dtype=np.int32) if pl > 0 else None,
                                timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN),
-                               temperature=temps[k], seed=seeds[k]))
+                               temperature=temps[k], seed=seeds[k], top_k=top_k, top_p=top_p))
         return out
 
     def _remote_done_rows(self, rows: np.ndarray) -> None:

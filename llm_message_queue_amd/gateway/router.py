@@ -32,7 +32,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..backend.engine import BackendEngine, Request
-from ..models.message import Message, MessageStatus, SamplingParseError, priority_name, sampling_from_metadata
+from ..models.message import (Message, MessageStatus, SamplingParseError, priority_name, sampling_from_metadata,
+                              truncation_from_metadata)
 from ..parallel import planner
 from ..parallel.comm import Comm, SoloComm
 from ..queue.core import QueueError
@@ -447,28 +448,45 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             if len(prompt) else np.zeros(1, dtype=np.int32)
         ck = conv_key(m.conversation_id) if self.kv_residency else -1
         hist, pre = self._dialog_context(m)
-        temp, seed = self._sampling(m)
+        temp, seed, top_k, top_p = self._sampling(m)
         return Request(req_id=m.handle, prompt=p, gen_tokens=self.gen_tokens, tier=tier, meta=m, conv=ck,
-                       history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed)
+                       history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed,
+                       top_k=top_k, top_p=top_p)
 
     @staticmethod
-    def _sampling(m: Message) -> Tuple[float, int]:
-        """The message's effective ``(temperature, seed)``
+    def _sampling(m: Message) -> Tuple[float, int, int, float]:
+        """The message's effective ``(temperature, seed, top_k, top_p)``
         (``metadata.sampling``), lenient: this path also serves messages
-        no route validated (the native ingress), so a bad value falls back
-        to greedy and is reported in ``metadata["sampling_error"]``.  A
-        message that asked for sampling gets the effective values written
-        back, so a client can replay it."""
+        no route validated (the native ingress), so a bad temperature or
+        seed falls back to greedy, a bad ``top_k`` / ``top_p`` turns the
+        truncation off, and either is reported in
+        ``metadata["sampling_error"]``.  A message that asked for sampling
+        gets the effective values written back, so a client can replay it:
+        ``top_k`` / ``top_p`` only where they are active (with a temperature,
+        and not off), so a message that named neither keeps exactly
+        ``{"temperature", "seed"}``."""
         md = m.metadata
         if not md or "sampling" not in md:
-            return 0.0, 0                         # greedy (the default traffic): the seed is never read
+            return 0.0, 0, 0, 1.0                 # greedy (the default traffic): the seed is never read
         try:
             temp, seed = sampling_from_metadata(md, m.id)
         except SamplingParseError as e:
             md["sampling_error"] = str(e)
             temp, seed = 0.0, sampling_from_metadata(None, m.id)[1]
-        md["sampling"] = {"temperature": temp, "seed": seed}
-        return temp, seed
+        try:
+            top_k, top_p = truncation_from_metadata(md)
+        except SamplingParseError as e:
+            md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
+            top_k, top_p = 0, 1.0
+        if temp <= 0:
+            top_k, top_p = 0, 1.0                 # (accepted, without effect)
+        eff = {"temperature": temp, "seed": seed}
+        if top_k > 0:
+            eff["top_k"] = top_k
+        if top_p < 1.0:
+            eff["top_p"] = top_p
+        md["sampling"] = eff
+        return temp, seed, top_k, top_p
 
     def _timeout_ns(self, m: Message) -> int:
         return int(m.timeout) if (self.inflight_timeout and m.timeout and m.timeout > 0) else 0

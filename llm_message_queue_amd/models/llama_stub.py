@@ -250,12 +250,16 @@ class LlamaStub:
     def forward(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 sample_idx: torch.Tensor, tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
                 small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
-                keys: Optional[torch.Tensor] = None, quant: bool = False) -> torch.Tensor:
+                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None) -> torch.Tensor:
         """One step over T tokens; returns greedy next-token ids for the rows
         in ``sample_idx`` (the last token of each request's chunk).  With
         ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
         (``ops.sampling.row_keys``) the head samples instead
-        (``ops.sample_head``: temperature sampling by Gumbel-max).
+        (``ops.sample_head``: temperature sampling by Gumbel-max).  ``trunc``
+        = (rows int64 [R] into the sampled rows, top_k int32 [R], top_p
+        float32 [R]): those rows ask for top-k / top-p and are drawn again,
+        from their own logits, by ``ops.truncated_head`` (the head over all
+        sampled rows runs as without it; their first draw is overwritten).
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -274,8 +278,14 @@ class LlamaStub:
                               small_cus=small_cus, quant=quant).index_select(0, sample_idx)
         hand = small_cus or not self.library_gemm
         if inv_temp is not None and keys is not None:
-            return self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
-                                        min_rows=1 if hand else 256)
+            out = self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
+                                       min_rows=1 if hand else 256)
+            if trunc is not None:
+                rows, top_k, top_p = trunc
+                out.index_copy_(0, rows, self.ops.truncated_head(
+                    sel.index_select(0, rows), self.lm_head, inv_temp.index_select(0, rows),
+                    keys.index_select(0, rows), top_k, top_p))
+            return out
         return self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
 
     @torch.no_grad()

@@ -329,7 +329,8 @@ def sampling_from_metadata(md: Any, message_id: str = "") -> tuple:
 
     ``temperature``: 0 (greedy, the default) or a number in [0.05, 2.0].
     ``seed``: an integer in [0, 2^63); without one, ``default_seed(message_id)``.
-    There is no top-k / top-p.  Raises ``SamplingParseError`` on anything else."""
+    ``top_k`` / ``top_p`` of the same object: :func:`truncation_from_metadata`.
+    Raises ``SamplingParseError`` on anything else."""
     sp = md.get("sampling") if isinstance(md, dict) else None
     if sp is None:
         return 0.0, default_seed(message_id)
@@ -347,6 +348,33 @@ def sampling_from_metadata(md: Any, message_id: str = "") -> tuple:
     elif isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < (1 << 63)):
         raise SamplingParseError("sampling.seed must be an integer in [0, 2^63)")
     return t, int(seed)
+
+
+TOP_K_MAX = 1023                     # (10 bits of the dispatch descriptor's flags column)
+
+
+def truncation_from_metadata(md: Any) -> tuple:
+    """``(top_k, top_p)`` of a message's ``metadata.sampling`` object.
+
+    ``top_k``: an integer, 0 (off, the default) or 1..1023.  ``top_p``: a
+    number in (0, 1], rounded to thousandths (so at least 0.001 after
+    rounding); 1.0 (the default) is off.  Both take effect only with a
+    ``temperature`` > 0.  Raises ``SamplingParseError`` on anything else."""
+    sp = md.get("sampling") if isinstance(md, dict) else None
+    if sp is None:
+        return 0, 1.0
+    if not isinstance(sp, dict):
+        raise SamplingParseError("sampling must be an object")
+    k = sp.get("top_k", 0)
+    if isinstance(k, bool) or not isinstance(k, int) or not (0 <= k <= TOP_K_MAX):
+        raise SamplingParseError(f"sampling.top_k must be an integer, 0 or in [1, {TOP_K_MAX}]")
+    p = sp.get("top_p", 1.0)
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p):
+        raise SamplingParseError("sampling.top_p must be a number")
+    permille = int(round(float(p) * 1000.0))
+    if not (0.0 < p <= 1.0) or permille < 1:
+        raise SamplingParseError("sampling.top_p must be in (0, 1] and at least 0.001")
+    return int(k), permille / 1000.0
 
 
 # --------------------------------------------------------------------------- conversation

@@ -8,7 +8,9 @@ element share a lane and the gate/up product never reaches HBM), ``qkv_rope``
 (qkv projection + RoPE + K/V-cache write), ``gemm_residual`` /
 ``gemm_residual_rms`` (``res += x·Wᵀ`` in place, the second with the next
 RMSNorm's row scales) and ``lm_head_argmax`` / ``lm_head_sample`` (the LM head
-with greedy or per-row temperature sampling, no logits tensor).  The first
+with greedy or per-row temperature sampling, no logits tensor;
+``sample_truncated`` is the top-k / top-p sampler over given logits,
+``csrc/kernels/sample_truncate_kernels.h``).  The first
 three take ``row_scale`` (the folded RMSNorm).  A step too small to fill the
 CUs runs split-K (:func:`split_plan`, :func:`split_all`) or, below
 ``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`; :func:`skinny_fp8`
@@ -124,7 +126,7 @@ def _scratch_entry(device, stream: int, name: str):
 
 def _scratch(device, stream: int, name: str, *specs):
     """The kernels' grow-only scratch, one entry per (device, stream) and user
-    ("split", "rms", "skinny", "head"): the entry's tensors, one per
+    ("split", "rms", "skinny", "head", "trunc"): the entry's tensors, one per
     ``(need, floor, alloc, dtype)`` in ``specs``.  A tensor of at least
     ``need`` elements is returned as it is, so launches in stream order share
     it and concurrent streams never do.  One too small is replaced by
@@ -653,6 +655,40 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, inv_temp: torch.Tensor, key
     _native.require_hipops().gemm_sample(x.data_ptr(), w.data_ptr(), M, N, K, inv_temp.data_ptr(), keys.data_ptr(),
                                          Mp, ws[0].data_ptr(), ws[1].data_ptr(), y.data_ptr(), stream)
     return y
+
+
+def sample_truncated(logits: torch.Tensor, inv_temp: torch.Tensor, keys: torch.Tensor, top_k: torch.Tensor,
+                     top_p: torch.Tensor, vocab: int = None, out: torch.Tensor = None) -> torch.Tensor:
+    """Top-k / top-p sampling over given bf16 ``logits`` [R][ld] -> int32 [R]
+    (``csrc/kernels/sample_truncate_kernels.h`` holds the contract,
+    ``ops.sampling.sample_truncated_reference`` is its twin): per row, top-k
+    then top-p select whole groups of equal values, and the pick is the argmax
+    of ``logit * inv_temp + G(key, n)`` over the kept columns.  ``vocab``:
+    the columns that count (default ld; the rest of a row is padding), ``ld %
+    8 == 0``.  ``inv_temp`` float32 [>= R] (> 0), ``keys`` 32-bit [>= R][2] =
+    ``ops.sampling.row_keys``, ``top_k`` int32 [>= R] (0: off), ``top_p``
+    float32 [>= R] (>= 1: off)."""
+    _check(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError("sample_truncated: logits must be [R][ld]")
+    R, ld = logits.shape
+    V = ld if vocab is None else int(vocab)
+    if not 0 < V <= ld or ld % 8:
+        raise ValueError(f"sample_truncated: needs 0 < vocab <= ld and ld % 8 == 0 (vocab={V} ld={ld})")
+    for t, n, dt in ((inv_temp, "inv_temp", (torch.float32,)), (top_k, "top_k", (torch.int32,)),
+                     (top_p, "top_p", (torch.float32,))):
+        if t.dtype not in dt or t.dim() != 1 or t.numel() < R or not t.is_contiguous() or t.device != logits.device:
+            raise ValueError(f"sample_truncated: {n} must be contiguous {dt[0]} [>= R] on the logits' device")
+    if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 2 or keys.shape[1] != 2 \
+            or keys.shape[0] < R or not keys.is_contiguous() or keys.device != logits.device:
+        raise ValueError("sample_truncated: keys must be contiguous 32-bit [>= R][2] on the logits' device")
+    y = out if out is not None else torch.empty(R, dtype=torch.int32, device=logits.device)
+    if y.dtype != torch.int32 or y.numel() < R or not y.is_contiguous() or y.device != logits.device:
+        raise ValueError("sample_truncated: out must be contiguous int32 [>= R] on the logits' device")
+    _native.require_hipops().sample_truncated(logits.data_ptr(), R, V, ld, inv_temp.data_ptr(), keys.data_ptr(),
+                                              top_k.data_ptr(), top_p.data_ptr(), y.data_ptr(),
+                                              torch.cuda.current_stream(logits.device).cuda_stream)
+    return y[:R]
 
 
 def sample_bits(keys: torch.Tensor, n0: int, count: int) -> torch.Tensor:

@@ -111,6 +111,26 @@ class HipOps:
         sc = torch.where(it != 0, lg.double() * it.double() - torch.log(e), lg.double())
         return torch.argmax(sc, dim=-1).to(torch.int32)
 
+    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p):
+        """Tokens of the LM head under top-k / top-p sampling (int32 [R];
+        ``ops.gemm.sample_truncated``) for the rows that ask for it.  Their
+        logits come from the 256x256 tile kernel's store epilogue whatever R
+        is -- no split-K, no skinny kernel -- so a row's logits are the bf16
+        rounding of the fp32 accumulators the fused head scores and do not
+        depend on who shares the step; a shape the tile kernel refuses takes
+        ``F.linear``.  The logits live in the grow-only scratch cache."""
+        from . import gemm as G
+        R, V = x.shape[0], w.shape[0]
+        if G.supported(R, V, x.shape[1]):
+            buf, = G._scratch(x.device, _stream(x), "trunc", (R * V, 0, torch.empty, torch.bfloat16))
+            lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
+        else:
+            lg = torch.nn.functional.linear(x, w)
+            if V % 8:
+                lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
+            lg = lg.contiguous()
+        return G.sample_truncated(lg, inv_temp.contiguous(), keys.contiguous(), top_k, top_p, vocab=V)
+
     def mlp_up(self, x: torch.Tensor, w_gu: torch.Tensor, fused: bool, min_fused_tokens: int) -> torch.Tensor:
         """silu(x·Wgᵀ) * (x·Wuᵀ).  ``fused``: ``w_gu`` is in swiglu order and
         steps of >= ``min_fused_tokens`` rows run the hand-written GEMM with
@@ -262,6 +282,17 @@ class RefOps:
         picks = torch.from_numpy(sample_reference(lg, it.cpu().numpy(), kk)).to(x.device)
         # a greedy row is exactly this class's greedy_head (bf16 logits)
         return torch.where(it != 0, picks, self.greedy_head(x, w, fused, min_rows))
+
+    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p):
+        """Reference of ``HipOps.truncated_head``: fp32 logits rounded to bf16,
+        then the numpy twin (``ops.sampling.sample_truncated_reference``)."""
+        from .sampling import sample_truncated_reference
+        R = x.shape[0]
+        lg = (x.float() @ w.float().t()).to(torch.bfloat16).float().cpu().numpy()
+        kk = keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
+        picks = sample_truncated_reference(lg, inv_temp[:R].cpu().numpy(), kk, top_k[:R].cpu().numpy(),
+                                           top_p[:R].cpu().numpy())
+        return torch.from_numpy(picks).to(x.device)
 
     def mlp_up(self, x, w_gu, fused: bool, min_fused_tokens: int):
         """Reference of ``HipOps.mlp_up`` (``w_gu`` in swiglu order if fused)."""

@@ -7,6 +7,10 @@ pure function of (request seed, index of the generated token, vocabulary
 column), so a request's tokens are reproducible whatever step, row, batch or
 GPU computed them.  The integer part (row keys, bits) equals the device's
 bit for bit; the Gumbel values are the same two-branch formula in float64.
+
+Top-k / top-p: :func:`truncation_keep` and :func:`sample_truncated_reference`
+are the twin of ``csrc/kernels/sample_truncate_kernels.h`` (the selection
+over whole groups of equal bf16 logits, then the same draw over what is kept).
 """
 from __future__ import annotations
 
@@ -81,6 +85,55 @@ def inv_temperature(temperature) -> np.ndarray:
     """float32 1 / T, 0 for a greedy row (T <= 0)."""
     t = np.asarray(temperature, dtype=np.float64)
     return np.where(t > 0, 1.0 / np.where(t > 0, t, 1.0), 0.0).astype(np.float32)
+
+
+def truncation_keep(logits_bf16, inv_temp, top_k, top_p) -> np.ndarray:
+    """bool [V]: the columns top-k then top-p keep of one row of bf16 logits
+    (an array of bf16-representable values), in float64 -- the twin of the
+    selection in ``csrc/kernels/sample_truncate_kernels.h``, which holds the
+    contract.  The distinct finite values in descending order are groups with
+    their counts; top-k keeps a group iff fewer than ``top_k`` columns lie in
+    the groups before it (0: off), top-p a group top-k kept iff the mass
+    ``count * exp((value - max) * inv_temp)`` of the kept groups before it is
+    below ``top_p`` times their total (>= 1: off); the first group always
+    stays.  A NaN or infinite logit is never kept."""
+    v = np.asarray(logits_bf16, dtype=np.float64).reshape(-1)
+    fin = np.isfinite(v)
+    if not fin.any():
+        return np.zeros(v.shape, dtype=bool)
+    vals, counts = np.unique(v[fin], return_counts=True)          # (-0 and +0 are one value)
+    vals, counts = vals[::-1], counts[::-1].astype(np.int64)
+    keep = np.ones(len(vals), dtype=bool)
+    if int(top_k) > 0:
+        keep = np.cumsum(counts) - counts < int(top_k)
+    tp = float(np.float32(top_p))
+    if tp < 1.0:
+        mass = np.where(keep, counts * np.exp((vals - vals[0]) * float(np.float32(inv_temp))), 0.0)
+        keep &= np.cumsum(mass) - mass < tp * mass.sum()
+    keep[0] = True
+    return fin & (v >= vals[keep].min())
+
+
+def sample_truncated_reference(logits, inv_temp, keys, top_k, top_p) -> np.ndarray:
+    """The reference of the truncated sampler: int32 [R] picks over bf16
+    ``logits`` [R][V], per row the argmax of ``logit * inv_temp + G`` over the
+    columns :func:`truncation_keep` keeps (float64 scores, ties to the lower
+    column; 0 for a row that keeps nothing).  ``top_k`` / ``top_p``: per row
+    or one value for all."""
+    lg = np.asarray(logits, dtype=np.float64)
+    R, V = lg.shape
+    it = np.broadcast_to(np.asarray(inv_temp, dtype=np.float32), (R,))
+    tk = np.broadcast_to(np.asarray(top_k, dtype=np.int64), (R,))
+    tp = np.broadcast_to(np.asarray(top_p, dtype=np.float32), (R,))
+    keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
+    cols = np.arange(V, dtype=np.uint32)
+    out = np.zeros(R, dtype=np.int32)
+    for r in range(R):
+        keep = truncation_keep(lg[r], it[r], tk[r], tp[r])
+        if keep.any():
+            sc = np.where(keep, lg[r], 0.0) * float(it[r]) + gumbel(keys[r:r + 1], cols)[0]
+            out[r] = np.where(keep, sc, -np.inf).argmax()
+    return out
 
 
 def sample_reference(logits, inv_temp, keys) -> np.ndarray:

@@ -415,6 +415,10 @@ def _skinny_args(fn: str, x: torch.Tensor, wshape, out: torch.Tensor, epi: int, 
     ``wshape`` [N][K], the split-K factor, the scratch and the row scale.
     Returns the launch's ``(M, N, K, epi, row-scale pointer, scratch pointer,
     S, stream)``."""
+    if out.device != x.device or (row_scale is not None and row_scale.device != x.device):
+        raise ValueError(f"{fn}: out / row_scale must be on x's device")
+    if x.device.type != "cuda":
+        raise ValueError(f"{fn}: x must be on a GPU")
     M, K = x.shape
     N = wshape[0]
     if wshape[1] != K or not 1 <= M <= SKINNY_CHUNKED_MAX_M or N % 128 or K % 128:
@@ -446,6 +450,8 @@ def skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epi: int, row_sc
     _check(x, "x")
     _check(w, "w")
     _check(out, "out")
+    if w.device != x.device:
+        raise ValueError("skinny: w must be on x's device")
     args = _skinny_args("skinny", x, w.shape, out, epi, row_scale, cus, splits)
     _native.require_hipops().skinny_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), *args)
     return out

@@ -160,6 +160,17 @@ def out_guarded(M, cols, rows=8, tail=256, device="cpu"):
     return Guarded(M, cols, rows, tail, device)
 
 
+def exact(g, ref, what):
+    """The guarded output holds no NaN (a read past x's rows or of the row
+    scales' padding), is the reference bit for bit, and nothing around it changed."""
+    y = g.out.cpu()
+    assert not torch.isnan(y.float()).any(), f"{what}: NaN"
+    bad = (bits(y) != bits(ref.to(torch.bfloat16))).nonzero()
+    assert bad.numel() == 0, f"{what}: {bad.shape[0]} wrong elements, first at {bad[0].tolist()}"
+    assert same_bits(y, ref)
+    assert g.intact(), f"{what}: wrote outside its [M][N]"
+
+
 # ----------------------------------------------------------------------------- SwiGLU
 @functools.lru_cache(maxsize=None)
 def swiglu_case(M, N, K, seed, row_scale=False):

@@ -34,15 +34,8 @@ def _split_counters_are_zero():
 
 
 def _exact(g, ref, what):
-    """The guarded output holds no NaN (a read past x's rows or of the row
-    scales' padding), is the reference bit for bit, and nothing around it changed."""
     torch.cuda.synchronize()
-    y = g.out.cpu()
-    assert not torch.isnan(y.float()).any(), f"{what}: NaN"
-    bad = (GC.bits(y) != GC.bits(ref.to(torch.bfloat16))).nonzero()
-    assert bad.numel() == 0, f"{what}: {bad.shape[0]} wrong elements, first at {bad[0].tolist()}"
-    assert GC.same_bits(y, ref)
-    assert g.intact(), f"{what}: wrote outside its [M][N]"
+    GC.exact(g, ref, what)
 
 
 # ----------------------------------------------------------------------------- a. STORE

@@ -19,6 +19,7 @@
 #include "gemm_kernels.h"
 #include "kv_migrate_kernels.h"
 #include "llama_kernels.h"
+#include "logprob_kernels.h"
 #include "sample_truncate_kernels.h"
 #include "skinny_kernels.h"
 #include "summarise_kernels.h"
@@ -415,6 +416,23 @@ static void sample_truncated(uintptr_t logits, int R, int V, int ld, uintptr_t i
   check_launch();
 }
 
+// out_lp[r] = the log-probability of token tok[r], then of the LP_TOP most likely columns out_id[r], of row r of
+// bf16 logits [R][ld] (columns < V): logprob_kernels.h holds the contract.  One block a row, grid-stride above
+// LP_MAX_BLOCKS.
+static void logprobs(uintptr_t logits, int R, int V, int ld, uintptr_t tok, uintptr_t out_lp, uintptr_t out_id,
+                     uintptr_t stream) {
+  const char* fn = "logprobs";
+  require_in(fn, R >= 0 && V > 0 && ld >= V && ld % 8 == 0, "needs R >= 0, 0 < V <= ld, ld % 8 == 0");
+  require_in(fn, logits != 0 && logits % 16 == 0, "logits must be 16-byte aligned");
+  require_in(fn, tok != 0 && out_lp != 0 && out_id != 0, "null pointer");
+  require_in(fn, tok % 4 == 0 && out_lp % 4 == 0 && out_id % 4 == 0, "per-row arrays must be 4-byte aligned");
+  if (R == 0) return;
+  hipLaunchKernelGGL(logprob_kernel, dim3(std::min(R, (int)LP_MAX_BLOCKS)), dim3(LP_THREADS), 0, S(stream),
+                     P<const uint16_t>(logits), R, V, ld, P<const int32_t>(tok), P<float>(out_lp),
+                     P<int32_t>(out_id));
+  check_launch();
+}
+
 static void row_rms(uintptr_t x, uintptr_t r, int T, int D, float eps, uintptr_t stream) {
   require(T >= 0 && D > 0 && D % 512 == 0, "row_rms expects D % 512 == 0");
   require(x % 16 == 0 && r % 4 == 0, "row_rms: misaligned pointers");
@@ -746,6 +764,10 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("out"), py::arg("stream"));
   m.def("sample_truncated", &sample_truncated, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"),
         py::arg("inv_temp"), py::arg("keys"), py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("stream"));
+  m.def("logprobs", &logprobs, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"), py::arg("tok"),
+        py::arg("out_lp"), py::arg("out_id"), py::arg("stream"));
+  m.attr("LP_TOP") = (int)LP_TOP;
+  m.attr("LP_MAX_BLOCKS") = (int)LP_MAX_BLOCKS;
   m.def("row_rms", &row_rms);
   m.attr("GEMM_EPI_STORE") = (int)GM_EPI_STORE;
   m.attr("GEMM_EPI_SWIGLU") = (int)GM_EPI_SWIGLU;

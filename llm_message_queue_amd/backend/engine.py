@@ -40,7 +40,7 @@ import torch
 
 from ..models.llama_stub import LlamaConfig, LlamaStub
 from ..ops.gemm import SKINNY_CHUNKED_MAX_M, row_scale_len
-from ..ops.sampling import inv_temperature, row_keys
+from ..ops.sampling import LP_TOP, inv_temperature, row_keys
 
 
 @dataclass
@@ -85,6 +85,14 @@ class Request:
     seed: int = 0
     top_k: int = 0
     top_p: float = 1.0
+    # log-probabilities (``csrc/kernels/logprob_kernels.h``): -1 = off, 0..5 =
+    # score every generated token, greedy or sampled (the engine always reads
+    # back all 5 alternatives; the caller trims to its n).  The results, one
+    # row per generated token, are set with ``out_tokens``
+    logprobs: int = -1
+    out_logprobs: Optional[np.ndarray] = None       # float32 [generated]
+    out_top_ids: Optional[np.ndarray] = None        # int32 [generated][5] (-1: no such alternative)
+    out_top_logprobs: Optional[np.ndarray] = None   # float32 [generated][5]
 
 
 @dataclass
@@ -148,10 +156,13 @@ class _Inflight:
     samp_slots: object = None     # int64 [S]: the slot each sampled row belongs to
     gidx: object = None           # int64 [S]: which generated token of its request each row is
     host_out: object = None       # pinned int32 [>= S]: the sampled ids, copied back behind the forward
+    lp_rows: object = None        # int64 [L]: the sampled rows scored by ``logprob_head`` (None: none)
+    host_lp: object = None        # pinned (float32 [>= L][6], int32 [>= L][5]): their results, copied back likewise
 
 
 class BackendEngine:
     MICRO_GRAPH_BUCKETS = (8, 16, 32, 64)
+    scores_logprobs = True        # False: an engine that runs no model leaves ``Request.out_logprobs`` None
 
     def __init__(self, model_cfg: LlamaConfig, slots: int = 256, max_ctx: int = 512,
                  token_budget: int = 2048, device="cuda", impl: str = "hip", seed: int = 0,
@@ -309,6 +320,11 @@ class BackendEngine:
         self.s_topp = np.ones(n_all, dtype=np.float32)      # top-p of a sampling slot (1: off)
         self.sampled_steps = 0                              # forwards that ended in the sampling head
         self.truncated_steps = 0                            # ... and drew a top-k / top-p row again (``truncated_head``)
+        self.s_logp = np.zeros(n_all, dtype=bool)           # the slot's request asks for log-probabilities
+        self.logprob_steps = 0                              # forwards that scored a row (``logprob_head``)
+        # host copy of every scored token's log-probability and alternatives,
+        # per slot, next to ``h_tokens`` (allocated with the first request that asks)
+        self.h_lp = self.h_top_ids = self.h_top_lp = None
         # host copy of every generated token id, per slot (written when the
         # step that sampled it is reaped; steps of one pool are reaped in
         # launch order, so a slot's next request never overwrites a row
@@ -347,11 +363,14 @@ class BackendEngine:
         # step k reuses step k - ring's buffer only once that one was reaped)
         ring = max(2, self.max_inflight)
         # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles,
-        #  and row index, top_k and top_p of its truncating rows)
-        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 5 * slots + 64 + 3 * row_scale_len(slots) + 4))
+        #  row index, top_k and top_p of its truncating rows, and the row index of a step's
+        #  log-probability rows)
+        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 6 * slots + 64 + 3 * row_scale_len(slots) + 4))
                       for _ in range(ring)]
         # sampled token ids copied back behind each forward (read at reap)
         self._out_pins = [self._alloc_pin(4 * self.n_all).view(torch.int32) for _ in range(ring)]
+        # log-probability rows copied back likewise
+        self._lp_pins = [self._alloc_lp_pin(self.n_all) for _ in range(ring)]
         # realtime micro-forwards: their own queue, staging, token gather source
         self._qm: Deque[_Inflight] = collections.deque()
         self._reaped_m: List[_Inflight] = []
@@ -369,9 +388,10 @@ class BackendEngine:
             # so it never grows (a grown pinned buffer frees the old one
             # behind the copies still queued from it)
             self._pins_m = [self._alloc_pin(4 * (11 * self.micro_budget + 2 * self.micro_slots + 64
-                                                 + 3 * row_scale_len(self.micro_slots) + 3 * self.micro_slots + 4))
+                                                 + 3 * row_scale_len(self.micro_slots) + 4 * self.micro_slots + 4))
                             for _ in range(mr)]
             self._out_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32) for _ in range(mr)]
+            self._lp_pins_m = [self._alloc_lp_pin(self.micro_slots) for _ in range(mr)]
         # segment-tiled MFMA attention on the HIP path (per-token otherwise)
         self.use_tiles = impl == "hip"
         self._state_pins = [self._alloc_pin(4 * slots) for _ in range(2)]
@@ -398,6 +418,10 @@ class BackendEngine:
     def _alloc_pin(self, nbytes: int) -> torch.Tensor:
         t = torch.empty(nbytes, dtype=torch.uint8)
         return t.pin_memory() if self.cuda else t
+
+    def _alloc_lp_pin(self, rows: int) -> tuple:
+        return (self._alloc_pin(4 * (1 + LP_TOP) * rows).view(torch.float32).view(rows, 1 + LP_TOP),
+                self._alloc_pin(4 * LP_TOP * rows).view(torch.int32).view(rows, LP_TOP))
 
     # ------------------------------------------------------------------ admission
     def free_slots(self) -> int:
@@ -573,6 +597,7 @@ class BackendEngine:
             r.micro = micro
             r.aborted = False
             r.out_tokens = None
+            r.out_logprobs = r.out_top_ids = r.out_top_logprobs = None
             base = 0
             s = self.conv_lru.pop(r.conv, None) if (r.conv >= 0 and not micro) else None
             if micro:
@@ -629,6 +654,12 @@ class BackendEngine:
             self.s_topk[s] = max(0, int(r.top_k)) if on else 0
             tp = float(r.top_p)
             self.s_topp[s] = tp if (on and 0.0 < tp < 1.0) else 1.0
+            # log-probabilities: greedy slots too
+            self.s_logp[s] = self.scores_logprobs and int(r.logprobs) >= 0
+            if self.s_logp[s] and self.h_lp is None:
+                self.h_lp = np.zeros((self.n_all, self.max_ctx), dtype=np.float32)
+                self.h_top_ids = np.zeros((self.n_all, self.max_ctx, LP_TOP), dtype=np.int32)
+                self.h_top_lp = np.zeros((self.n_all, self.max_ctx, LP_TOP), dtype=np.float32)
             # prefill order key: realtime-lane tiers sort before everything else
             self.s_seq[s] = self._admit_seq - (1 << 48 if 0 <= r.tier < self.fast_tiers else 0)
             self._admit_seq += 1
@@ -1041,7 +1072,12 @@ class BackendEngine:
         # decode micro-forward with a sampling row takes the eager path.
         temp = self.s_temp[samp_slots]
         sampling = bool(S) and bool((temp > 0).any())
-        if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling:
+        # rows that ask for log-probabilities, greedy or sampling: scored again
+        # on their own path (``logprob_head``).  The captured graphs hold no
+        # such path either
+        lrows = np.flatnonzero(self.s_logp[samp_slots]) if S else np.zeros(0, dtype=np.int64)
+        L = len(lrows)
+        if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling and not L:
             Tb = next((b for b in self.MICRO_GRAPH_BUCKETS if b >= T and b in self._mg), 0)
             if Tb:
                 return self._launch_micro_graph(Tb, t0, t_mono, pos, slot, samp_slots, dec_src)
@@ -1058,11 +1094,16 @@ class BackendEngine:
             if sampling else ()
         R = len(trows)
         o_trn = o_smp + 3 * Sp
-        buf = np.empty(o_trn + 3 * R, dtype=np.int32)
+        # the log-probability rows behind the truncation block (nothing when
+        # there are none: the buffer is then what it is without the feature)
+        o_lgp = o_trn + 3 * R
+        buf = np.empty(o_lgp + L, dtype=np.int32)
         if R:
             buf[o_trn:o_trn + R] = trows
             buf[o_trn + R:o_trn + 2 * R] = self.s_topk[samp_slots[trows]]
-            buf[o_trn + 2 * R:] = self.s_topp[samp_slots[trows]].view(np.int32)
+            buf[o_trn + 2 * R:o_lgp] = self.s_topp[samp_slots[trows]].view(np.int32)
+        if L:
+            buf[o_lgp:] = lrows
         if sampling:
             buf[o_til + 4 * NT:o_trn] = 0
             buf[o_smp:o_smp + S] = inv_temperature(temp).view(np.int32)
@@ -1078,6 +1119,7 @@ class BackendEngine:
         nbytes = buf.nbytes
         sid = self.micro_id if micro else self.step_id
         pins, outs = (self._pins_m, self._out_pins_m) if micro else (self._pins, self._out_pins)
+        host_lp = (self._lp_pins_m if micro else self._lp_pins)[sid % len(pins)] if L else None
         k = sid % len(pins)
         pin = pins[k]
         if pin.numel() < nbytes:
@@ -1106,20 +1148,29 @@ class BackendEngine:
                     skw["trunc"] = (d[o_trn:o_trn + R].long(), d[o_trn + R:o_trn + 2 * R],
                                     d[o_trn + 2 * R:o_trn + 3 * R].view(torch.float32))
                     self.truncated_steps += 1
+            if L:
+                skw["logp"] = d[o_lgp:o_lgp + L].long()
+                self.logprob_steps += 1
             ev0 = self._start_event()
             te = time.perf_counter_ns()
             fwd = self._micro_forward if micro else self.model.forward
             out = fwd(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til, n_dec=D, **skw)
+            if L:
+                out, lp, ids = out
             self.host_ns[2] += time.perf_counter_ns() - te
             if not micro:
                 self._census(T)
             # the sampled ids come back behind the forward (read at reap)
             host_out[:S].copy_(out, non_blocking=True)
+            if L:
+                host_lp[0][:L].copy_(lp, non_blocking=True)
+                host_lp[1][:L].copy_(ids, non_blocking=True)
             ev = self._end_event(T, ev0 is not None)
-        return self._retire(sid, T, n_pre, n_dec, S, samp_slots, out, host_out, ev, ev0, t0, t_mono, micro)
+        return self._retire(sid, T, n_pre, n_dec, S, samp_slots, out, host_out, ev, ev0, t0, t_mono, micro,
+                            lp_rows=lrows if L else None, host_lp=host_lp)
 
     def _retire(self, sid: int, T: int, n_pre: int, n_dec: int, S: int, ss, out, host_out, ev, ev0,
-                t0: float, t_mono: int, micro: bool, graph: bool = False) -> bool:
+                t0: float, t_mono: int, micro: bool, graph: bool = False, lp_rows=None, host_lp=None) -> bool:
         """The deterministic bookkeeping behind every enqueued forward (a
         serving step, an eager micro-forward or a graph replay): every sampled
         slot gets one token, finished requests leave their slots, and the
@@ -1154,7 +1205,7 @@ class BackendEngine:
                 self.free.append(x)
         self.s_active[done] = False
         f = _Inflight(sid, ev, T, n_pre, n_dec, completed, firsts, t0, out, t_mono, ev0, micro=micro,
-                      samp_slots=ss, gidx=gidx, host_out=host_out)
+                      samp_slots=ss, gidx=gidx, host_out=host_out, lp_rows=lp_rows, host_lp=host_lp)
         if micro:
             self._prev_out_m = out
             self._qm.append(f)
@@ -1277,12 +1328,25 @@ class BackendEngine:
             ss = f.samp_slots
             ok = f.gidx < self.max_ctx
             self.h_tokens[ss[ok], f.gidx[ok]] = f.host_out.numpy()[:len(ss)][ok]
+            if f.lp_rows is not None:
+                # ... and the scored rows' log-probabilities, under the same guard
+                keep = ok[f.lp_rows]
+                rows = f.lp_rows[keep]
+                lp = f.host_lp[0].numpy()[:len(keep)][keep]
+                self.h_lp[ss[rows], f.gidx[rows]] = lp[:, 0]
+                self.h_top_lp[ss[rows], f.gidx[rows]] = lp[:, 1:]
+                self.h_top_ids[ss[rows], f.gidx[rows]] = f.host_lp[1].numpy()[:len(keep)][keep]
         for r in f.firsts:
             if not r.aborted:
                 r.first_token_ns = now
         for r in f.completed:
             r.done_ns = now
             r.out_tokens = self.h_tokens[r.slot, :min(r.generated, self.max_ctx)].copy()
+            if r.logprobs >= 0 and self.h_lp is not None:
+                n = len(r.out_tokens)
+                r.out_logprobs = self.h_lp[r.slot, :n].copy()
+                r.out_top_ids = self.h_top_ids[r.slot, :n].copy()
+                r.out_top_logprobs = self.h_top_lp[r.slot, :n].copy()
         if self.page is not None and not self.cuda and not self.fault.get("drop_heartbeat") and not micro:
             self.page.write_host(self.inflight(), self.free_slots(), f.T, f.step)
         return f

@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ..ops.sampling import LP_TOP
+
 # --------------------------------------------------------------------------- descriptors
 K_DISPATCH, K_DONE, K_FAIL = 1, 2, 3     # K_FAIL: an evacuating backend hands a request back
 K_MIGRATE = 4       # [kind, conv lo/hi, dest]: to a conversation's home GPU -- send its KV to dest this tick
@@ -30,6 +32,7 @@ DESC_HDR = 20       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/h
 #                    dialog history length, decision - enq (us), processing timeout (ms),
 #                    sampling temperature (float32 bits), sampling seed lo/hi];
 #                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN | top_k << 10 | top_p permille << 20
+#                            | LOGPROBS
 KV_MIGRATE = 1 << 8     # descriptor flag: hold the turn until its KV arrives from the home GPU
 DIALOG_TURN = 1 << 9    # descriptor flag: a conversation turn -- its generated ids go back with K_DONE
 # the sampling truncation of a request with a temperature, 10 bits each of the
@@ -50,6 +53,64 @@ def unpack_truncation(flags: int) -> tuple:
     """``(top_k, top_p)`` of a flags column value."""
     pm = (int(flags) >> TOPP_SHIFT) & TRUNC_MASK
     return (int(flags) >> TOPK_SHIFT) & TRUNC_MASK, (pm / 1000.0 if 0 < pm < 1000 else 1.0)
+
+
+# descriptor flag: score the request's tokens (``Request.logprobs``).  Only the
+# flag travels: the serving GPU always returns all alternatives and the origin,
+# which knows the message's n, trims
+LOGPROBS = 1 << 30
+# serving GPU -> origin, ahead of the request's K_DONE (same FIFO): the
+# log-probabilities of a request dispatched with LOGPROBS, LP_WORDS int32 a
+# generated token -- id, lp (float32 bits), 5 alternative ids, their 5 lps --
+# as one stream cut into rows of at most ``cap`` payload words: [kind, handle
+# lo/hi, origin, offset (col 4), words of this row lo/hi, words in all (col 7)
+# lo/hi, -, words of this row (col 10)]
+K_LOGP = 9
+LP_WORDS = 2 + 2 * LP_TOP
+
+
+def pack_logprob_stream(tokens, lp, top_ids, top_lp) -> np.ndarray:
+    """The int32 stream of a request's log-probability results (LP_WORDS a
+    token; floats as their bits)."""
+    n = len(tokens)
+    st = np.empty((n, LP_WORDS), dtype=np.int32)
+    st[:, 0] = np.asarray(tokens, dtype=np.int32)
+    st[:, 1] = np.ascontiguousarray(lp, dtype=np.float32).view(np.int32)
+    st[:, 2:2 + LP_TOP] = np.asarray(top_ids, dtype=np.int32).reshape(n, LP_TOP)
+    st[:, 2 + LP_TOP:] = np.ascontiguousarray(top_lp, dtype=np.float32).view(np.int32).reshape(n, LP_TOP)
+    return st.reshape(-1)
+
+
+def unpack_logprob_stream(stream: np.ndarray) -> tuple:
+    """``(tokens int32 [n], lp float32 [n], top_ids int32 [n][5], top_lp
+    float32 [n][5])`` of a stream of :func:`pack_logprob_stream`."""
+    st = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1, LP_WORDS)
+    return (st[:, 0].copy(), st[:, 1].copy().view(np.float32), st[:, 2:2 + LP_TOP].copy(),
+            np.ascontiguousarray(st[:, 2 + LP_TOP:]).view(np.float32))
+
+
+def logprob_chunks(total: int, cap: int) -> list:
+    """``(offset, words)`` of the K_LOGP rows that carry a stream of
+    ``total`` words, ``cap`` payload words a row."""
+    return [(off, min(cap, total - off)) for off in range(0, total, cap)]
+
+
+def fill_logprob_row(row: np.ndarray, stream: np.ndarray, off: int, n: int) -> None:
+    """Words ``off .. off + n`` of ``stream`` into the K_LOGP row ``row``."""
+    row[10] = n
+    row[DESC_HDR:DESC_HDR + n] = stream[off:off + n]
+
+
+def take_logprob_rows(parts: dict, src: int, rows: np.ndarray) -> None:
+    """K_LOGP rows from ``src`` into ``parts``: (source, handle) -> the
+    stream so far (whole once every row of it has arrived; rows may come in
+    several exchanges)."""
+    for h, off, n, total, row in zip(_get64(rows, 1).tolist(), rows[:, 4].tolist(), rows[:, 10].tolist(),
+                                     rows[:, 7].tolist(), rows):
+        buf = parts.get((src, h))
+        if buf is None or len(buf) != total:
+            buf = parts[(src, h)] = np.zeros(total, dtype=np.int32)
+        buf[off:off + n] = row[DESC_HDR:DESC_HDR + n]
 
 
 def conv_key(conversation_id: str) -> int:

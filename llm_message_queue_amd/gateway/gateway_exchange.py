@@ -26,9 +26,11 @@ import numpy as np
 from ..backend.engine import Request
 from ..models.message import Message, MessageStatus
 from ..parallel import planner
+from ..ops.sampling import LP_TOP
 from .descriptors import (DESC_HDR, DIALOG_TURN, FAIL_UNTOUCHED, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE, K_FAIL,
-                          K_HIST, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, _get64, _put64, conv_key, pack_truncation,
-                          unpack_truncation)
+                          K_HIST, K_LOGP, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, LOGPROBS, _get64, _put64, conv_key,
+                          fill_logprob_row, logprob_chunks, pack_logprob_stream, pack_truncation, take_logprob_rows,
+                          unpack_logprob_stream, unpack_truncation)
 
 HIST_LEN_BITS = 20      # descriptor col 14: dialog history length | (compressed-context length << 20)
 from .latency import P_PLAN_LOCAL, P_PLAN_REMOTE
@@ -199,13 +201,20 @@ class ExchangeMixin:
                 _put64(d, 7, a[:, 3])
                 toks = self._done_tok[j]
                 if toks:
-                    # a dialog turn's generated ids ride in its record's payload
-                    for k, h in enumerate(a[:, 0].tolist()):
-                        t = toks.pop(h, None)
+                    # a dialog turn's generated ids ride in its K_DONE record's payload (not in the
+                    # K_LOGP records queued ahead of it under the same handle)
+                    for k, (h, kind) in enumerate(zip(a[:, 0].tolist(), a[:, 4].tolist())):
+                        t = toks.pop(h, None) if kind == K_DONE else None
                         if t is not None:
                             n = min(len(t), cap)
                             d[k, 10] = n
                             d[k, DESC_HDR:DESC_HDR + n] = np.asarray(t[:n], dtype=np.int32)
+                for k in np.flatnonzero(a[:, 4] == K_LOGP).tolist():
+                    # (handle, offset, words, words in all, K_LOGP): a chunk of a log-probability stream
+                    h, off, n, total = a[k, :4].tolist()
+                    fill_logprob_row(d[k], self._done_lp[j][h], off, n)
+                    if off + n >= total:
+                        del self._done_lp[j][h]
             self._done_owed[j] = self._done_owed[j][done_for[j]:]
             if hist_rows is not None:
                 extra = np.concatenate([extra, hist_rows])
@@ -257,12 +266,17 @@ class ExchangeMixin:
                         self._hist_wait[(r.meta[0], r.meta[1])] = r
                     else:
                         fresh.append(r)
+            lrows = g[kinds == K_LOGP]
+            if len(lrows):                            # (ahead of their K_DONE, which attaches them)
+                take_logprob_rows(self._lp_parts, src, lrows)
             done = g[kinds == K_DONE]
             if len(done):
                 self._remote_done_rows(done)
             for row in g[kinds == K_FAIL]:
+                self._lp_parts.pop((src, int(_get64(row.reshape(1, -1), 1)[0])), None)
                 self._remote_fail(row)
             for row in g[(kinds == K_TIMEOUT) | (kinds == K_CANCELLED)]:
+                self._lp_parts.pop((src, int(_get64(row.reshape(1, -1), 1)[0])), None)
                 self._remote_abort(row)
             can = g[kinds == K_CANCEL]
             if len(can):
@@ -366,8 +380,8 @@ class ExchangeMixin:
             small[k, 4] = min(0x7FFFFFFF, max(0, (m.popped_ns - m.enqueued_at) // 1000)) \
                 if (m.popped_ns and m.enqueued_at) else 0
             small[k, 5] = min(0x7FFFFFFF, self._timeout_ns(m) // 1_000_000)
-            temp[k], seed[k], top_k, top_p = self._sampling(m)
-            small[k, 2] |= pack_truncation(top_k, top_p)
+            temp[k], seed[k], top_k, top_p, logprobs = self._sampling(m)
+            small[k, 2] |= pack_truncation(top_k, top_p) | (LOGPROBS if logprobs >= 0 else 0)
         buf[:, 0] = K_DISPATCH
         _put64(buf, 1, v[:, 0])
         buf[:, 3] = origin
@@ -485,18 +499,32 @@ class ExchangeMixin:
                                history=np.zeros(hl, dtype=np.int32) if hl > 0 else None,
                                prefix=np.zeros(pl, dtype=np.int32) if pl > 0 else None,
                                timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN),
-                               temperature=temps[k], seed=seeds[k], top_k=top_k, top_p=top_p))
+                               temperature=temps[k], seed=seeds[k], top_k=top_k, top_p=top_p,
+                               logprobs=LP_TOP if fl & LOGPROBS else -1))
         return out
+
+    def _owe_logprobs(self, origin: int, handle: int, r: Request) -> None:
+        """Queue the K_LOGP rows of a foreign request that asked for
+        log-probabilities (the caller queues its K_DONE right behind)."""
+        stream = pack_logprob_stream(r.out_tokens, r.out_logprobs, r.out_top_ids, r.out_top_logprobs)
+        if not len(stream):
+            return
+        self._done_lp[origin][handle] = stream
+        for off, n in logprob_chunks(len(stream), self.prompt_cap):
+            self._done_owed[origin].append((handle, off, n, len(stream), K_LOGP))
 
     def _remote_done_rows(self, rows: np.ndarray) -> None:
         """K_DONE rows: my requests another GPU finished."""
         for k, (h, gpu, adm, done, nt) in enumerate(zip(
                 _get64(rows, 1).tolist(), rows[:, 3].tolist(), _get64(rows, 5).tolist(), _get64(rows, 7).tolist(),
                 rows[:, 10].tolist())):
+            lp = self._lp_parts.pop((int(gpu), h), None)
             m = self.remote_out.pop(h, None)
             if m is None:
                 continue
             self.inflight_by_tier[m.tier] -= 1
+            if lp is not None and not self.table.cancelled(m):
+                self._attach_generation(m, *unpack_logprob_stream(lp))
             if self.table.cancelled(m):       # cancelled after that GPU launched its last token
                 self._finish_cancel(m, done - adm, dispatched=True)
                 continue

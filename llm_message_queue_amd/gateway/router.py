@@ -32,8 +32,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..backend.engine import BackendEngine, Request
-from ..models.message import (Message, MessageStatus, SamplingParseError, priority_name, sampling_from_metadata,
-                              truncation_from_metadata)
+from ..models.message import (Message, MessageStatus, SamplingParseError, generation_record, logprobs_from_metadata,
+                              priority_name, sampling_from_metadata, truncation_from_metadata)
 from ..parallel import planner
 from ..parallel.comm import Comm, SoloComm
 from ..queue.core import QueueError
@@ -168,6 +168,10 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         self._done_pub: List[int] = [0] * self.world      # records of _done_owed announced this tick
         # generated ids of the dialog turns in _done_owed (origin -> handle -> ids)
         self._done_tok: Dict[int, Dict[int, np.ndarray]] = {r: {} for r in range(self.world)}
+        # log-probability streams of the K_LOGP rows in _done_owed (origin -> handle -> int32 stream),
+        # and the chunks received for my own requests ((source, handle) -> stream so far)
+        self._done_lp: Dict[int, Dict[int, np.ndarray]] = {r: {} for r in range(self.world)}
+        self._lp_parts: Dict[Tuple[int, int], np.ndarray] = {}
         # dialog histories owed to the GPUs this router dispatched turns to
         # (sent one tick later as K_HIST rows, counted in that tick's load vector)
         self._hist_out: Dict[int, List[Tuple[int, np.ndarray, np.ndarray]]] = {}
@@ -448,26 +452,28 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             if len(prompt) else np.zeros(1, dtype=np.int32)
         ck = conv_key(m.conversation_id) if self.kv_residency else -1
         hist, pre = self._dialog_context(m)
-        temp, seed, top_k, top_p = self._sampling(m)
+        temp, seed, top_k, top_p, logprobs = self._sampling(m)
         return Request(req_id=m.handle, prompt=p, gen_tokens=self.gen_tokens, tier=tier, meta=m, conv=ck,
                        history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed,
-                       top_k=top_k, top_p=top_p)
+                       top_k=top_k, top_p=top_p, logprobs=logprobs)
 
     @staticmethod
-    def _sampling(m: Message) -> Tuple[float, int, int, float]:
-        """The message's effective ``(temperature, seed, top_k, top_p)``
-        (``metadata.sampling``), lenient: this path also serves messages
-        no route validated (the native ingress), so a bad temperature or
-        seed falls back to greedy, a bad ``top_k`` / ``top_p`` turns the
-        truncation off, and either is reported in
+    def _sampling(m: Message) -> Tuple[float, int, int, float, int]:
+        """The message's effective ``(temperature, seed, top_k, top_p,
+        logprobs)`` (``metadata.sampling``), lenient: this path also serves
+        messages no route validated (the native ingress), so a bad
+        temperature or seed falls back to greedy, a bad ``top_k`` / ``top_p``
+        turns the truncation off, a bad ``logprobs`` turns the
+        log-probabilities off (-1), and each is reported in
         ``metadata["sampling_error"]``.  A message that asked for sampling
         gets the effective values written back, so a client can replay it:
         ``top_k`` / ``top_p`` only where they are active (with a temperature,
-        and not off), so a message that named neither keeps exactly
-        ``{"temperature", "seed"}``."""
+        and not off) and ``logprobs`` only where the message named it, so a
+        message that named none of them keeps exactly ``{"temperature",
+        "seed"}``."""
         md = m.metadata
         if not md or "sampling" not in md:
-            return 0.0, 0, 0, 1.0                 # greedy (the default traffic): the seed is never read
+            return 0.0, 0, 0, 1.0, -1             # greedy (the default traffic): the seed is never read
         try:
             temp, seed = sampling_from_metadata(md, m.id)
         except SamplingParseError as e:
@@ -478,6 +484,11 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         except SamplingParseError as e:
             md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
             top_k, top_p = 0, 1.0
+        try:
+            logprobs = logprobs_from_metadata(md)
+        except SamplingParseError as e:
+            md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
+            logprobs = -1
         if temp <= 0:
             top_k, top_p = 0, 1.0                 # (accepted, without effect)
         eff = {"temperature": temp, "seed": seed}
@@ -485,8 +496,23 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             eff["top_k"] = top_k
         if top_p < 1.0:
             eff["top_p"] = top_p
+        if logprobs >= 0:
+            eff["logprobs"] = logprobs
         md["sampling"] = eff
-        return temp, seed, top_k, top_p
+        return temp, seed, top_k, top_p, logprobs
+
+    @staticmethod
+    def _attach_generation(m: Message, tokens, lp, top_ids, top_lp) -> None:
+        """``metadata.generation`` of a message that asked for
+        log-probabilities, from its last attempt's results, trimmed to its
+        own ``n`` (nothing for a message that did not ask, or an engine that
+        ran no model)."""
+        sp = m.metadata.get("sampling") if isinstance(m.metadata, dict) else None
+        n = sp.get("logprobs") if isinstance(sp, dict) else None
+        if tokens is None or lp is None or isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            return
+        k = min(len(tokens), len(lp))
+        m.metadata["generation"] = generation_record(tokens[:k], lp[:k], top_ids[:k], top_lp[:k], n)
 
     def _timeout_ns(self, m: Message) -> int:
         return int(m.timeout) if (self.inflight_timeout and m.timeout and m.timeout > 0) else 0
@@ -669,9 +695,13 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
                     self._finish_cancel(m, r.done_ns - r.admitted_ns, dispatched=True)
                     continue
                 self._remember_dialog(m, self.rank, r.out_tokens)
+                self._attach_generation(m, r.out_tokens, getattr(r, "out_logprobs", None),
+                                        getattr(r, "out_top_ids", None), getattr(r, "out_top_logprobs", None))
                 self._complete(m, r.done_ns - r.admitted_ns)
             else:
                 origin, handle, tier = self.foreign.pop(r.req_id)
+                if getattr(r, "out_logprobs", None) is not None and r.out_tokens is not None:
+                    self._owe_logprobs(origin, handle, r)     # (ahead of the K_DONE: FIFO)
                 self._done_owed[origin].append((handle, tier, r.admitted_ns, r.done_ns, K_DONE))
                 if (r.conv >= 0 or r.dialog) and r.out_tokens is not None:   # a dialog turn: its ids go home
                     self._done_tok[origin][handle] = r.out_tokens

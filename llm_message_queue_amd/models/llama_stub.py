@@ -250,7 +250,7 @@ class LlamaStub:
     def forward(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 sample_idx: torch.Tensor, tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
                 small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
-                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None) -> torch.Tensor:
+                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None, logp=None):
         """One step over T tokens; returns greedy next-token ids for the rows
         in ``sample_idx`` (the last token of each request's chunk).  With
         ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
@@ -260,6 +260,11 @@ class LlamaStub:
         float32 [R]): those rows ask for top-k / top-p and are drawn again,
         from their own logits, by ``ops.truncated_head`` (the head over all
         sampled rows runs as without it; their first draw is overwritten).
+        ``logp`` (int64 [L] rows into the sampled rows, sampling or greedy):
+        those rows ask for log-probabilities; the result is then ``(tokens,
+        lp float32 [L][6], ids int32 [L][5])`` with ``ops.logprob_head``'s
+        scores of the tokens finally chosen, after the truncation overwrite
+        (the tokens themselves are what they are without it).
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -285,8 +290,12 @@ class LlamaStub:
                 out.index_copy_(0, rows, self.ops.truncated_head(
                     sel.index_select(0, rows), self.lm_head, inv_temp.index_select(0, rows),
                     keys.index_select(0, rows), top_k, top_p))
+        else:
+            out = self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
+        if logp is None:
             return out
-        return self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
+        lp, ids = self.ops.logprob_head(sel.index_select(0, logp), self.lm_head, out.index_select(0, logp))
+        return out, lp, ids
 
     @torch.no_grad()
     def hidden(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,

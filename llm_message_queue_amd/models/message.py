@@ -377,6 +377,45 @@ def truncation_from_metadata(md: Any) -> tuple:
     return int(k), permille / 1000.0
 
 
+from ..ops.sampling import LP_TOP as LOGPROBS_MAX  # noqa: E402  (the alternatives the kernel reports)
+
+
+def logprobs_from_metadata(md: Any) -> int:
+    """``logprobs`` of a message's ``metadata.sampling`` object: -1 (off, the
+    default: the key is absent) or an integer ``n`` in 0..5 -- return every
+    generated token with its log-probability and, for ``n`` > 0, the ``n``
+    most likely tokens at each position.  It works with or without a
+    ``temperature``.  Raises ``SamplingParseError`` on anything else."""
+    sp = md.get("sampling") if isinstance(md, dict) else None
+    if sp is None:
+        return -1
+    if not isinstance(sp, dict):
+        raise SamplingParseError("sampling must be an object")
+    if "logprobs" not in sp:
+        return -1
+    n = sp["logprobs"]
+    if isinstance(n, bool) or not isinstance(n, int) or not (0 <= n <= LOGPROBS_MAX):
+        raise SamplingParseError(f"sampling.logprobs must be an integer in [0, {LOGPROBS_MAX}]")
+    return int(n)
+
+
+def generation_record(tokens, token_logprobs, top_ids, top_logprobs, n: int) -> Dict[str, Any]:
+    """``metadata.generation`` of a completed message that asked for
+    ``logprobs = n``: the generated tokens, their log-probabilities and, for
+    ``n`` > 0, the ``n`` most likely tokens of each position (fewer where the
+    distribution had fewer).  A non-finite value is written as None (JSON
+    ``null``)."""
+    def num(x):
+        x = float(x)
+        return x if math.isfinite(x) else None
+
+    out = {"tokens": [int(t) for t in tokens], "token_logprobs": [num(x) for x in token_logprobs]}
+    if n > 0:
+        out["top_logprobs"] = [[{"token": int(i), "logprob": num(x)} for i, x in zip(ids[:n], lps[:n]) if i >= 0]
+                               for ids, lps in zip(top_ids, top_logprobs)]
+    return out
+
+
 # --------------------------------------------------------------------------- conversation
 class Conversation:
     """`message.go:93-109`, plus the summary state produced by the

@@ -10,7 +10,9 @@ element share a lane and the gate/up product never reaches HBM), ``qkv_rope``
 RMSNorm's row scales) and ``lm_head_argmax`` / ``lm_head_sample`` (the LM head
 with greedy or per-row temperature sampling, no logits tensor;
 ``sample_truncated`` is the top-k / top-p sampler over given logits,
-``csrc/kernels/sample_truncate_kernels.h``).  The first
+``csrc/kernels/sample_truncate_kernels.h``, ``token_logprobs`` scores a
+token and the most likely alternatives over given logits,
+``csrc/kernels/logprob_kernels.h``).  The first
 three take ``row_scale`` (the folded RMSNorm).  A step too small to fill the
 CUs runs split-K (:func:`split_plan`, :func:`split_all`) or, below
 ``SKINNY_*_MAX_M`` rows, on the skinny kernel (:func:`skinny`; :func:`skinny_fp8`
@@ -695,6 +697,44 @@ def sample_truncated(logits: torch.Tensor, inv_temp: torch.Tensor, keys: torch.T
                                               top_k.data_ptr(), top_p.data_ptr(), y.data_ptr(),
                                               torch.cuda.current_stream(logits.device).cuda_stream)
     return y[:R]
+
+
+from .sampling import LP_TOP  # noqa: E402  (alternatives a row)
+
+
+def token_logprobs(logits: torch.Tensor, tok: torch.Tensor, vocab: int = None, out_lp: torch.Tensor = None,
+                   out_id: torch.Tensor = None):
+    """Log-probabilities over given bf16 ``logits`` [R][ld] -> ``(lp float32
+    [R][1 + LP_TOP], ids int32 [R][LP_TOP])`` (``csrc/kernels/
+    logprob_kernels.h`` holds the contract, ``ops.sampling.logprob_reference``
+    is its twin): per row ``log_softmax`` over the finite columns, of token
+    ``tok[r]`` first (-inf for a token out of range or on a non-finite column),
+    then of the LP_TOP most likely columns ``ids`` (ties to the lower column;
+    -1 / -inf where the row has fewer).  ``vocab``: the columns that count
+    (default ld; the rest of a row is padding), ``ld % 8 == 0``.  ``tok`` int32
+    [>= R]."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("token_logprobs: logits must be bfloat16 [R][ld] on a GPU")
+    R, ld = logits.shape
+    if R:                                               # (an empty tensor has no address to check)
+        _check(logits, "logits")
+    V = ld if vocab is None else int(vocab)
+    if not 0 < V <= ld or ld % 8:
+        raise ValueError(f"token_logprobs: needs 0 < vocab <= ld and ld % 8 == 0 (vocab={V} ld={ld})")
+    if tok.dtype != torch.int32 or tok.dim() != 1 or tok.numel() < R or not tok.is_contiguous() \
+            or tok.device != logits.device:
+        raise ValueError("token_logprobs: tok must be contiguous int32 [>= R] on the logits' device")
+    lp = out_lp if out_lp is not None else torch.empty((R, 1 + LP_TOP), dtype=torch.float32, device=logits.device)
+    ids = out_id if out_id is not None else torch.empty((R, LP_TOP), dtype=torch.int32, device=logits.device)
+    if lp.dtype != torch.float32 or lp.numel() < R * (1 + LP_TOP) or not lp.is_contiguous() \
+            or lp.device != logits.device:
+        raise ValueError("token_logprobs: out_lp must be contiguous float32 [>= R][6] on the logits' device")
+    if ids.dtype != torch.int32 or ids.numel() < R * LP_TOP or not ids.is_contiguous() or ids.device != logits.device:
+        raise ValueError("token_logprobs: out_id must be contiguous int32 [>= R][5] on the logits' device")
+    if R:
+        _native.require_hipops().logprobs(logits.data_ptr(), R, V, ld, tok.data_ptr(), lp.data_ptr(), ids.data_ptr(),
+                                          torch.cuda.current_stream(logits.device).cuda_stream)
+    return lp.view(-1)[:R * (1 + LP_TOP)].view(R, 1 + LP_TOP), ids.view(-1)[:R * LP_TOP].view(R, LP_TOP)
 
 
 def sample_bits(keys: torch.Tensor, n0: int, count: int) -> torch.Tensor:

@@ -131,6 +131,26 @@ class HipOps:
             lg = lg.contiguous()
         return G.sample_truncated(lg, inv_temp.contiguous(), keys.contiguous(), top_k, top_p, vocab=V)
 
+    def logprob_head(self, x, w, tok):
+        """Log-probabilities of the LM head for the rows that ask for them:
+        ``(lp float32 [L][6], ids int32 [L][5])`` of ``ops.gemm.
+        token_logprobs`` -- the token ``tok`` (int32 [L]) first, then the 5
+        most likely.  The logits come as ``truncated_head``'s do (the tile
+        kernel's store epilogue whatever L is, ``F.linear`` for a shape it
+        refuses), in a scratch entry of their own, so a row's result depends
+        on nothing but the row."""
+        from . import gemm as G
+        R, V = x.shape[0], w.shape[0]
+        if G.supported(R, V, x.shape[1]):
+            buf, = G._scratch(x.device, _stream(x), "logp", (R * V, 0, torch.empty, torch.bfloat16))
+            lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
+        else:
+            lg = torch.nn.functional.linear(x, w)
+            if V % 8:
+                lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
+            lg = lg.contiguous()
+        return G.token_logprobs(lg, tok.to(torch.int32).contiguous(), vocab=V)
+
     def mlp_up(self, x: torch.Tensor, w_gu: torch.Tensor, fused: bool, min_fused_tokens: int) -> torch.Tensor:
         """silu(x·Wgᵀ) * (x·Wuᵀ).  ``fused``: ``w_gu`` is in swiglu order and
         steps of >= ``min_fused_tokens`` rows run the hand-written GEMM with
@@ -293,6 +313,15 @@ class RefOps:
         picks = sample_truncated_reference(lg, inv_temp[:R].cpu().numpy(), kk, top_k[:R].cpu().numpy(),
                                            top_p[:R].cpu().numpy())
         return torch.from_numpy(picks).to(x.device)
+
+    def logprob_head(self, x, w, tok):
+        """Reference of ``HipOps.logprob_head``: fp32 logits rounded to bf16,
+        then the numpy twin in float64 (``ops.sampling.logprob_reference``)."""
+        from .sampling import logprob_reference
+        lg = (x.float() @ w.float().t()).to(torch.bfloat16).float().cpu().numpy()
+        lp, ids = logprob_reference(lg, tok.cpu().numpy())
+        return (torch.from_numpy(lp.astype("float32")).to(x.device),
+                torch.from_numpy(ids.astype("int32")).to(x.device))
 
     def mlp_up(self, x, w_gu, fused: bool, min_fused_tokens: int):
         """Reference of ``HipOps.mlp_up`` (``w_gu`` in swiglu order if fused)."""

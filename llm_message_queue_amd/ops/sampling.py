@@ -11,6 +11,10 @@ bit for bit; the Gumbel values are the same two-branch formula in float64.
 Top-k / top-p: :func:`truncation_keep` and :func:`sample_truncated_reference`
 are the twin of ``csrc/kernels/sample_truncate_kernels.h`` (the selection
 over whole groups of equal bf16 logits, then the same draw over what is kept).
+
+Log-probabilities: :func:`logprob_reference` is the float64 twin of
+``csrc/kernels/logprob_kernels.h`` and :func:`logprob_bound` the bound on the
+device's distance from it, derived there.
 """
 from __future__ import annotations
 
@@ -134,6 +138,61 @@ def sample_truncated_reference(logits, inv_temp, keys, top_k, top_p) -> np.ndarr
             sc = np.where(keep, lg[r], 0.0) * float(it[r]) + gumbel(keys[r:r + 1], cols)[0]
             out[r] = np.where(keep, sc, -np.inf).argmax()
     return out
+
+
+# alternatives a row: the package's one copy of csrc/kernels/logprob_kernels.h's LP_TOP (the parser's
+# upper limit, the engine's buffers and the K_LOGP stream all take it from here)
+LP_TOP = 5
+
+
+def logprob_reference(logits, tok) -> tuple:
+    """The twin of ``csrc/kernels/logprob_kernels.h``, which holds the
+    contract, in float64: ``(lp float64 [L][1 + LP_TOP], ids int64
+    [L][LP_TOP])`` over bf16 ``logits`` [L][V] (an array of bf16-representable
+    values) and the chosen tokens ``tok`` [L].  Per row the candidates are the
+    finite columns, ``lp(n) = (l[n] - m) - log(sum exp(l - m))`` with ``m``
+    their maximum; ``lp[:, 0]`` is the token's (-inf for a token outside [0,
+    V) or on a column that is no candidate), ``lp[:, 1:]`` those of the LP_TOP
+    largest candidates ``ids`` (ties to the lower column; -1 / -inf where the
+    row has fewer)."""
+    lg = np.asarray(logits, dtype=np.float64)
+    L, V = lg.shape
+    tok = np.broadcast_to(np.asarray(tok, dtype=np.int64), (L,))
+    lp = np.full((L, 1 + LP_TOP), -np.inf, dtype=np.float64)
+    ids = np.full((L, LP_TOP), -1, dtype=np.int64)
+    for r in range(L):
+        fin = np.isfinite(lg[r])
+        if not fin.any():
+            continue
+        m = lg[r][fin].max()
+        d = np.where(fin, lg[r], m) - m
+        logz = np.log(np.exp(d[fin]).sum())
+        cand = np.flatnonzero(fin)
+        order = cand[np.argsort(-lg[r][cand], kind="stable")[:LP_TOP]]     # (stable: a tie keeps the lower column)
+        ids[r, :len(order)] = order
+        lp[r, 1:1 + len(order)] = d[order] - logz
+        t = int(tok[r])
+        if 0 <= t < V and fin[t]:
+            lp[r, 0] = d[t] - logz
+    return lp, ids
+
+
+def logprob_bound(V: int, span: float = 128.0) -> float:
+    """The bound on ``|device - twin|`` of a log-probability, in nats, for a
+    row of ``V`` columns and a column within ``span`` of the row's maximum
+    (``|l - m| <= span``; an fp32 ``exp`` is 0 from 104 on, so the default
+    covers every column with a probability above 0).  The derivation, term by
+    term from the kernel's order of operations, is in
+    ``csrc/kernels/logprob_kernels.h``."""
+    import math
+    u = 2.0 ** -24
+    logv = math.log(max(int(V), 2))
+    depth = 8 * ((int(V) + 2047) // 2048) + 8         # a thread's columns, 6 shuffle levels, 2 for the waves
+    rho = math.expm1((logv + 2.0 + depth) * math.log1p(u)) + int(V) * 2.0 ** -126
+    return (-math.log1p(-rho)                         # log Z' against log Z
+            + 2.0 * u * (logv + rho)                  # logf, 1 ulp
+            + span * u                                # d = fl(l - m)
+            + (span + logv + 1.0) * u)                # lp = fl(d - log Z)
 
 
 def sample_reference(logits, inv_temp, keys) -> np.ndarray:

@@ -20,6 +20,7 @@
 #include "kv_migrate_kernels.h"
 #include "llama_kernels.h"
 #include "logprob_kernels.h"
+#include "penalty_kernels.h"
 #include "sample_truncate_kernels.h"
 #include "skinny_kernels.h"
 #include "summarise_kernels.h"
@@ -433,6 +434,54 @@ static void logprobs(uintptr_t logits, int R, int V, int ld, uintptr_t tok, uint
   check_launch();
 }
 
+// Edit rows of bf16 logits [R][ld] (columns < V) in place by the presence / frequency / repetition penalties of
+// their token histories: penalty_kernels.h holds the contract.  hist int32 [n_slots][stride], spans int32 [R][4] =
+// (slot, from, split, end), params fp32 [R][3] = (pp, fp, rp).  One block a row, grid-stride above PEN_MAX_BLOCKS.
+static void penalise(uintptr_t logits, int R, int V, int ld, uintptr_t hist, int n_slots, int stride, uintptr_t spans,
+                     uintptr_t params, uintptr_t stream) {
+  const char* fn = "penalise";
+  require_in(fn, R >= 0 && V > 0 && ld >= V && ld % 8 == 0, "needs R >= 0, 0 < V <= ld, ld % 8 == 0");
+  require_in(fn, n_slots > 0 && stride > 0 && stride <= PEN_HIST_MAX, "needs a history table of 1..PEN_HIST_MAX columns");
+  require_in(fn, logits != 0 && logits % 2 == 0, "logits must be 2-byte aligned");
+  require_in(fn, hist != 0 && spans != 0 && params != 0, "null pointer");
+  require_in(fn, hist % 4 == 0 && spans % 4 == 0 && params % 4 == 0, "arrays must be 4-byte aligned");
+  if (R == 0) return;
+  hipLaunchKernelGGL(penalise_kernel, dim3(std::min(R, (int)PEN_MAX_BLOCKS)), dim3(PEN_THREADS), 0, S(stream),
+                     P<uint16_t>(logits), R, V, ld, P<const int32_t>(hist), n_slots, stride, P<const int32_t>(spans),
+                     P<const float>(params));
+  check_launch();
+}
+
+// out[r] = the greedy pick over row r of (edited) bf16 logits [R][ld], for the rows with inv_temp[r] <= 0
+// (inv_temp 0: every row); penalty_kernels.h.
+static void penalised_argmax(uintptr_t logits, int R, int V, int ld, uintptr_t inv_temp, uintptr_t out,
+                             uintptr_t stream) {
+  const char* fn = "penalised_argmax";
+  require_in(fn, R >= 0 && V > 0 && ld >= V && ld % 8 == 0, "needs R >= 0, 0 < V <= ld, ld % 8 == 0");
+  require_in(fn, logits != 0 && logits % 16 == 0, "logits must be 16-byte aligned");
+  require_in(fn, out != 0 && out % 4 == 0 && inv_temp % 4 == 0, "per-row arrays must be non-null and 4-byte aligned");
+  if (R == 0) return;
+  hipLaunchKernelGGL(penalised_argmax_kernel, dim3(std::min(R, (int)PEN_MAX_BLOCKS)), dim3(PEN_THREADS), 0, S(stream),
+                     P<const uint16_t>(logits), R, V, ld, P<const float>(inv_temp), P<int32_t>(out));
+  check_launch();
+}
+
+// hist[slot[t]][pos[t]] = tok[t] for the token rows t = rows[0..Q) of a forward of T tokens (int64 tok, int32 pos /
+// slot): the device-side token history of penalty_kernels.h.
+static void history_record(uintptr_t hist, int n_slots, int stride, uintptr_t tok, uintptr_t pos, uintptr_t slot, int T,
+                           uintptr_t rows, int Q, uintptr_t stream) {
+  const char* fn = "history_record";
+  require_in(fn, n_slots > 0 && stride > 0 && T >= 0 && Q >= 0, "needs n_slots, stride > 0 and T, Q >= 0");
+  require_in(fn, (int64_t)n_slots * stride < (int64_t)1 << 31, "history table too large");
+  require_in(fn, hist != 0 && tok != 0 && pos != 0 && slot != 0 && rows != 0, "null pointer");
+  require_in(fn, hist % 4 == 0 && tok % 8 == 0 && pos % 4 == 0 && slot % 4 == 0 && rows % 4 == 0, "alignment");
+  if (Q == 0 || T == 0) return;
+  hipLaunchKernelGGL(history_record_kernel, dim3(std::min((Q + PEN_THREADS - 1) / PEN_THREADS, 64)),
+                     dim3(PEN_THREADS), 0, S(stream), P<int32_t>(hist), n_slots, stride, P<const int64_t>(tok),
+                     P<const int32_t>(pos), P<const int32_t>(slot), T, P<const int32_t>(rows), Q);
+  check_launch();
+}
+
 static void row_rms(uintptr_t x, uintptr_t r, int T, int D, float eps, uintptr_t stream) {
   require(T >= 0 && D > 0 && D % 512 == 0, "row_rms expects D % 512 == 0");
   require(x % 16 == 0 && r % 4 == 0, "row_rms: misaligned pointers");
@@ -768,6 +817,14 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("out_lp"), py::arg("out_id"), py::arg("stream"));
   m.attr("LP_TOP") = (int)LP_TOP;
   m.attr("LP_MAX_BLOCKS") = (int)LP_MAX_BLOCKS;
+  m.def("penalise", &penalise, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"), py::arg("hist"),
+        py::arg("n_slots"), py::arg("stride"), py::arg("spans"), py::arg("params"), py::arg("stream"));
+  m.def("penalised_argmax", &penalised_argmax, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"),
+        py::arg("inv_temp"), py::arg("out"), py::arg("stream"));
+  m.def("history_record", &history_record, py::arg("hist"), py::arg("n_slots"), py::arg("stride"), py::arg("tok"),
+        py::arg("pos"), py::arg("slot"), py::arg("T"), py::arg("rows"), py::arg("Q"), py::arg("stream"));
+  m.attr("PEN_HIST_MAX") = (int)PEN_HIST_MAX;
+  m.attr("PEN_MAX_BLOCKS") = (int)PEN_MAX_BLOCKS;
   m.def("row_rms", &row_rms);
   m.attr("GEMM_EPI_STORE") = (int)GM_EPI_STORE;
   m.attr("GEMM_EPI_SWIGLU") = (int)GM_EPI_SWIGLU;

@@ -37,8 +37,8 @@ from fastapi.responses import JSONResponse, Response
 from ..balancer.load_balancer import Endpoint, LoadBalancerError
 from ..models.message import (ConversationNotFound, Message, MessageStatus,
                               PriorityParseError, format_time, level_priority_from_name, logprobs_from_metadata,
-                              parse_priority,
-                              priority_name, sampling_from_metadata, truncation_from_metadata)
+                              parse_priority, penalties_from_metadata, priority_name, sampling_from_metadata,
+                              truncation_from_metadata)
 from ..scheduler.resource_scheduler import Resource, ResourceError
 from ..utils.metrics import CONTENT_TYPE_LATEST
 from .security import guard_from_config, redact_config
@@ -254,6 +254,7 @@ def create_app(gw_app, allowed_origins: Optional[List[str]] = None,
             sampling_from_metadata(m.metadata, m.id)      # (the gateway resolves it; here only: reject bad values)
             truncation_from_metadata(m.metadata)
             logprobs_from_metadata(m.metadata)
+            penalties_from_metadata(m.metadata)
         except (ValueError, PriorityParseError, TypeError) as e:
             return _err(400, f"Invalid message format: {e}")
         bad = await _enqueue(m)

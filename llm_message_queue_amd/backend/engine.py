@@ -40,7 +40,7 @@ import torch
 
 from ..models.llama_stub import LlamaConfig, LlamaStub
 from ..ops.gemm import SKINNY_CHUNKED_MAX_M, row_scale_len
-from ..ops.sampling import LP_TOP, inv_temperature, row_keys
+from ..ops.sampling import LP_TOP, PEN_HIST_MAX, inv_temperature, row_keys
 
 
 @dataclass
@@ -93,6 +93,14 @@ class Request:
     out_logprobs: Optional[np.ndarray] = None       # float32 [generated]
     out_top_ids: Optional[np.ndarray] = None        # int32 [generated][5] (-1: no such alternative)
     out_top_logprobs: Optional[np.ndarray] = None   # float32 [generated][5]
+    # penalties (``csrc/kernels/penalty_kernels.h``), greedy or sampling,
+    # applied before temperature and truncation: presence / frequency over the
+    # tokens this attempt generated, repetition over those and the message's
+    # own prompt (0 / 0 / 1: off).  Earlier turns of a dialog, resident or
+    # replayed, are outside the window
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
 
 
 @dataclass
@@ -162,6 +170,7 @@ class _Inflight:
 
 class BackendEngine:
     MICRO_GRAPH_BUCKETS = (8, 16, 32, 64)
+    runs_model = True             # False: an engine that runs no model ignores a request's penalties
     scores_logprobs = True        # False: an engine that runs no model leaves ``Request.out_logprobs`` None
 
     def __init__(self, model_cfg: LlamaConfig, slots: int = 256, max_ctx: int = 512,
@@ -199,6 +208,8 @@ class BackendEngine:
         # An empty mode follows ``realtime_step_tokens`` (> 0: "cap").
         self.rt_step_tokens = int(realtime_step_tokens)
         mode = realtime_mode or ("cap" if self.rt_step_tokens > 0 else "off")
+        if max_ctx > PEN_HIST_MAX:
+            raise ValueError(f"max_ctx {max_ctx} exceeds the penalty kernel's history of {PEN_HIST_MAX} tokens")
         if mode not in ("off", "cap", "micro"):
             raise ValueError(f"realtime_mode must be off / cap / micro, not {mode!r}")
         if mode != "cap":
@@ -322,6 +333,14 @@ class BackendEngine:
         self.truncated_steps = 0                            # ... and drew a top-k / top-p row again (``truncated_head``)
         self.s_logp = np.zeros(n_all, dtype=bool)           # the slot's request asks for log-probabilities
         self.logprob_steps = 0                              # forwards that scored a row (``logprob_head``)
+        # penalties: the slot's (presence, frequency, repetition) and the
+        # position its window starts at (``s_plen - n_own``: the message's own
+        # capped prompt, not a resident or replayed context before it)
+        self.s_pen = np.zeros(n_all, dtype=bool)
+        self.s_penp = np.zeros((n_all, 3), dtype=np.float32)
+        self.s_pfrom = np.zeros(n_all, dtype=np.int64)
+        self.penalised_steps = 0                            # forwards that drew a penalised row (``penalised_head``)
+        self.d_hist = None                                  # the device-side token history (first penalised request)
         # host copy of every scored token's log-probability and alternatives,
         # per slot, next to ``h_tokens`` (allocated with the first request that asks)
         self.h_lp = self.h_top_ids = self.h_top_lp = None
@@ -364,8 +383,9 @@ class BackendEngine:
         ring = max(2, self.max_inflight)
         # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles,
         #  row index, top_k and top_p of its truncating rows, and the row index of a step's
-        #  log-probability rows)
-        self._pins = [self._alloc_pin(4 * (7 * self.token_budget + 6 * slots + 64 + 3 * row_scale_len(slots) + 4))
+        #  log-probability rows, and a penalised step's block: 10 words per penalised row and the token
+        #  rows to record)
+        self._pins = [self._alloc_pin(4 * (8 * self.token_budget + 16 * slots + 64 + 3 * row_scale_len(slots) + 4))
                       for _ in range(ring)]
         # sampled token ids copied back behind each forward (read at reap)
         self._out_pins = [self._alloc_pin(4 * self.n_all).view(torch.int32) for _ in range(ring)]
@@ -387,8 +407,8 @@ class BackendEngine:
             # gather rows (<= 3T) and ~one 1-token tile per row (4T) -- sized
             # so it never grows (a grown pinned buffer frees the old one
             # behind the copies still queued from it)
-            self._pins_m = [self._alloc_pin(4 * (11 * self.micro_budget + 2 * self.micro_slots + 64
-                                                 + 3 * row_scale_len(self.micro_slots) + 4 * self.micro_slots + 4))
+            self._pins_m = [self._alloc_pin(4 * (12 * self.micro_budget + 2 * self.micro_slots + 64
+                                                 + 3 * row_scale_len(self.micro_slots) + 14 * self.micro_slots + 4))
                             for _ in range(mr)]
             self._out_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32) for _ in range(mr)]
             self._lp_pins_m = [self._alloc_lp_pin(self.micro_slots) for _ in range(mr)]
@@ -594,6 +614,7 @@ class BackendEngine:
             r.prompt = np.asarray(r.prompt[:plen], dtype=np.int64) % self.cfg.vocab
             if len(r.prompt) == 0:
                 r.prompt = np.zeros(1, dtype=np.int64)
+            n_own = len(r.prompt)                             # (before any replay is prepended)
             r.micro = micro
             r.aborted = False
             r.out_tokens = None
@@ -660,6 +681,25 @@ class BackendEngine:
                 self.h_lp = np.zeros((self.n_all, self.max_ctx), dtype=np.float32)
                 self.h_top_ids = np.zeros((self.n_all, self.max_ctx, LP_TOP), dtype=np.int32)
                 self.h_top_lp = np.zeros((self.n_all, self.max_ctx, LP_TOP), dtype=np.float32)
+            # penalties, greedy slots too; a value off its range is off
+            self.s_pen[s] = False
+            if (r.presence_penalty or r.frequency_penalty or r.repetition_penalty != 1.0) and self.runs_model:
+                pv = np.array([r.presence_penalty, r.frequency_penalty, r.repetition_penalty], dtype=np.float32)
+                if np.isfinite(pv).all() and pv[2] > 0:
+                    self.s_penp[s] = pv
+                    self.s_pen[s] = bool(pv[0] != 0 or pv[1] != 0 or pv[2] != 1)
+                    self.s_pfrom[s] = base + n - n_own
+            if self.s_pen[s] and self.d_hist is None:
+                # the device-side token history, indexed [slot][absolute
+                # position] (``penalty_kernels.h``).  Not filled: a fill would
+                # be queued on this call's stream and nothing orders it with
+                # the records on the pools' streams.  None is needed, and no
+                # synchronisation beyond stream order: a slot's new occupant
+                # records every position of its window, in forwards of the
+                # slot's own pool and stream, before the first head that reads
+                # it; nothing outside a window is ever read, and the micro
+                # pool has slots and a stream of its own
+                self.d_hist = torch.empty((self.n_all, self.max_ctx), dtype=torch.int32, device=self.device)
             # prefill order key: realtime-lane tiers sort before everything else
             self.s_seq[s] = self._admit_seq - (1 << 48 if 0 <= r.tier < self.fast_tiers else 0)
             self._admit_seq += 1
@@ -1077,7 +1117,21 @@ class BackendEngine:
         # such path either
         lrows = np.flatnonzero(self.s_logp[samp_slots]) if S else np.zeros(0, dtype=np.int64)
         L = len(lrows)
-        if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling and not L:
+        # penalised slots: every token row of theirs in this forward is recorded
+        # in the device history, and their sampled rows are drawn again on
+        # their own path (``penalised_head``), greedy rows first.  Eager in the
+        # micro pool as well.  A row that also truncates leaves ``trunc``
+        qrows = np.flatnonzero(self.s_pen[slot]) if self.d_hist is not None else np.zeros(0, dtype=np.int64)
+        Q = len(qrows)
+        prows = np.flatnonzero(self.s_pen[samp_slots]) if (Q and S) else np.zeros(0, dtype=np.int64)
+        P = len(prows)
+        n_greedy = 0
+        if P:
+            hot = temp[prows] > 0
+            n_greedy = int(P - hot.sum())
+            prows = np.concatenate([prows[~hot], prows[hot]])
+        if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling and not L \
+                and not Q:
             Tb = next((b for b in self.MICRO_GRAPH_BUCKETS if b >= T and b in self._mg), 0)
             if Tb:
                 return self._launch_micro_graph(Tb, t0, t_mono, pos, slot, samp_slots, dec_src)
@@ -1090,20 +1144,37 @@ class BackendEngine:
         Sp = row_scale_len(S) if sampling else 0
         # rows that also ask for top-k / top-p: their indices into the sampled
         # rows, top_k and top_p (float32 bits) behind the keys, same copy
-        trows = np.flatnonzero((temp > 0) & ((self.s_topk[samp_slots] > 0) | (self.s_topp[samp_slots] < 1))) \
-            if sampling else ()
+        trows = np.flatnonzero((temp > 0) & ((self.s_topk[samp_slots] > 0) | (self.s_topp[samp_slots] < 1))
+                               & ~self.s_pen[samp_slots]) if sampling else ()
         R = len(trows)
         o_trn = o_smp + 3 * Sp
         # the log-probability rows behind the truncation block (nothing when
         # there are none: the buffer is then what it is without the feature)
         o_lgp = o_trn + 3 * R
-        buf = np.empty(o_lgp + L, dtype=np.int32)
+        # the penalty block behind the log-probability rows (empty when
+        # unused): per penalised row its index, span (slot, from, split, end),
+        # parameters, top_k and top_p, then the token rows to record
+        o_pen = o_lgp + L
+        buf = np.empty(o_pen + 10 * P + Q, dtype=np.int32)
+        if Q:
+            buf[o_pen + 10 * P:] = qrows
+        if P:
+            ps = samp_slots[prows]
+            buf[o_pen:o_pen + P] = prows
+            sp = buf[o_pen + P:o_pen + 5 * P].reshape(P, 4)
+            sp[:, 0] = ps
+            sp[:, 1] = self.s_pfrom[ps]
+            sp[:, 2] = self.s_plen[ps]
+            sp[:, 3] = self.s_plen[ps] + self.s_gen[ps]
+            buf[o_pen + 5 * P:o_pen + 8 * P] = self.s_penp[ps].view(np.int32).reshape(-1)
+            buf[o_pen + 8 * P:o_pen + 9 * P] = self.s_topk[ps]
+            buf[o_pen + 9 * P:o_pen + 10 * P] = self.s_topp[ps].view(np.int32)
         if R:
             buf[o_trn:o_trn + R] = trows
             buf[o_trn + R:o_trn + 2 * R] = self.s_topk[samp_slots[trows]]
             buf[o_trn + 2 * R:o_lgp] = self.s_topp[samp_slots[trows]].view(np.int32)
         if L:
-            buf[o_lgp:] = lrows
+            buf[o_lgp:o_pen] = lrows
         if sampling:
             buf[o_til + 4 * NT:o_trn] = 0
             buf[o_smp:o_smp + S] = inv_temperature(temp).view(np.int32)
@@ -1151,6 +1222,13 @@ class BackendEngine:
             if L:
                 skw["logp"] = d[o_lgp:o_lgp + L].long()
                 self.logprob_steps += 1
+            if Q:
+                skw["pen"] = (self.d_hist, d[o_pen + 10 * P:o_pen + 10 * P + Q], d[o_pen:o_pen + P].long(),
+                              d[o_pen + P:o_pen + 5 * P].view(P, 4),
+                              d[o_pen + 5 * P:o_pen + 8 * P].view(torch.float32).view(P, 3),
+                              d[o_pen + 8 * P:o_pen + 9 * P], d[o_pen + 9 * P:o_pen + 10 * P].view(torch.float32),
+                              n_greedy)
+                self.penalised_steps += int(P > 0)
             ev0 = self._start_event()
             te = time.perf_counter_ns()
             fwd = self._micro_forward if micro else self.model.forward

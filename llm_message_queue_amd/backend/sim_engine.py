@@ -63,7 +63,8 @@ class _SimStart:
 
 
 class SimEngine(BackendEngine):
-    scores_logprobs = False                        # no model runs: a request's ``logprobs`` is ignored
+    runs_model = False                             # no model runs: a request's penalties are ignored
+    scores_logprobs = False                        # ... and so is its ``logprobs``
 
     def __init__(self, *, speed: float = 1.0, tile_ms: float = 2.5, base_ms: float = 1.5,
                  slots: int = 1536, max_ctx: int = 512, token_budget: int = 4096, max_inflight: int = 2,
@@ -85,7 +86,8 @@ class SimEngine(BackendEngine):
         return (self.base_ms + self.tile_ms * -(-int(T) // 256)) / self.speed
 
     @staticmethod
-    def _forward(tok, pos, slot, samp, tiles=None, n_dec=0, inv_temp=None, keys=None, trunc=None, logp=None):
+    def _forward(tok, pos, slot, samp, tiles=None, n_dec=0, inv_temp=None, keys=None, trunc=None, logp=None,
+                 pen=None):
         return torch.zeros(int(samp.shape[0]), dtype=torch.int32)
 
     def warm_shapes(self, sizes=None) -> int:

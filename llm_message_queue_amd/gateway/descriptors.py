@@ -31,6 +31,7 @@ K_HIST = 8
 DESC_HDR = 20       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/hi, gen, plen, flags, conv lo/hi,
 #                    dialog history length, decision - enq (us), processing timeout (ms),
 #                    sampling temperature (float32 bits), sampling seed lo/hi];
+#                    tier = tier | presence, frequency, repetition penalties << 4 (``pack_penalties``);
 #                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN | top_k << 10 | top_p permille << 20
 #                            | LOGPROBS
 KV_MIGRATE = 1 << 8     # descriptor flag: hold the turn until its KV arrives from the home GPU
@@ -59,6 +60,36 @@ def unpack_truncation(flags: int) -> tuple:
 # flag travels: the serving GPU always returns all alternatives and the origin,
 # which knows the message's n, trims
 LOGPROBS = 1 << 30
+# the penalties of a request, in hundredths above the tier (1..4, bits 0-3) of
+# a K_DISPATCH row's tier column: presence in bits 4-12 and frequency in bits
+# 13-21 (signed 9 bits, -200..200), repetition - 100 in bits 22-29 (signed 8
+# bits, -50..100).  A request without penalties leaves them zero.  The
+# engine's floats are float32(hundredths / 100) on every GPU.
+TIER_MASK = 0xF
+PRES_SHIFT, FREQ_SHIFT, REP_SHIFT = 4, 13, 22
+
+
+def _hundredths(v: float, lo: int, hi: int, off: int) -> int:
+    h = int(round(float(v) * 100.0)) if np.isfinite(v) else off
+    return h if lo <= h <= hi else off
+
+
+def pack_penalties(presence: float, frequency: float, repetition: float) -> int:
+    """The tier-column bits of the three penalties (0: none)."""
+    return ((_hundredths(presence, -200, 200, 0) & 0x1FF) << PRES_SHIFT) \
+        | ((_hundredths(frequency, -200, 200, 0) & 0x1FF) << FREQ_SHIFT) \
+        | (((_hundredths(repetition, 50, 200, 100) - 100) & 0xFF) << REP_SHIFT)
+
+
+def unpack_penalties(col: int) -> tuple:
+    """``(tier, presence, frequency, repetition)`` of a tier column value."""
+    def signed(v, bits):
+        return v - (1 << bits) if v >> (bits - 1) else v
+    c = int(col)
+    if c < 0:                                        # (a message dispatched without a tier: nothing is packed)
+        return c, 0.0, 0.0, 1.0
+    return (c & TIER_MASK, signed((c >> PRES_SHIFT) & 0x1FF, 9) / 100.0, signed((c >> FREQ_SHIFT) & 0x1FF, 9) / 100.0,
+            (signed((c >> REP_SHIFT) & 0xFF, 8) + 100) / 100.0)
 # serving GPU -> origin, ahead of the request's K_DONE (same FIFO): the
 # log-probabilities of a request dispatched with LOGPROBS, LP_WORDS int32 a
 # generated token -- id, lp (float32 bits), 5 alternative ids, their 5 lps --

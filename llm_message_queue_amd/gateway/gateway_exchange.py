@@ -29,7 +29,8 @@ from ..parallel import planner
 from ..ops.sampling import LP_TOP
 from .descriptors import (DESC_HDR, DIALOG_TURN, FAIL_UNTOUCHED, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE, K_FAIL,
                           K_HIST, K_LOGP, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, LOGPROBS, _get64, _put64, conv_key,
-                          fill_logprob_row, logprob_chunks, pack_logprob_stream, pack_truncation, take_logprob_rows,
+                          fill_logprob_row, logprob_chunks, pack_logprob_stream, pack_penalties, pack_truncation,
+                          take_logprob_rows, unpack_penalties,
                           unpack_logprob_stream, unpack_truncation)
 
 HIST_LEN_BITS = 20      # descriptor col 14: dialog history length | (compressed-context length << 20)
@@ -380,8 +381,10 @@ class ExchangeMixin:
             small[k, 4] = min(0x7FFFFFFF, max(0, (m.popped_ns - m.enqueued_at) // 1000)) \
                 if (m.popped_ns and m.enqueued_at) else 0
             small[k, 5] = min(0x7FFFFFFF, self._timeout_ns(m) // 1_000_000)
-            temp[k], seed[k], top_k, top_p, logprobs = self._sampling(m)
+            temp[k], seed[k], top_k, top_p, logprobs, pens = self._sampling(m)
             small[k, 2] |= pack_truncation(top_k, top_p) | (LOGPROBS if logprobs >= 0 else 0)
+            if m.tier >= 0:
+                small[k, 0] |= pack_penalties(*pens)
         buf[:, 0] = K_DISPATCH
         _put64(buf, 1, v[:, 0])
         buf[:, 3] = origin
@@ -490,6 +493,7 @@ class ExchangeMixin:
             self._next_req += 1
             hl, pl = hv & mask, hv >> HIST_LEN_BITS
             top_k, top_p = unpack_truncation(fl)
+            tier, pres, freq, rep = unpack_penalties(tier)
             # the dialog context's LENGTH travels here (a resident turn only
             # needs it to check its KV is current); a turn that must replay
             # waits for the real tokens (K_HIST, next exchange), which replace
@@ -500,7 +504,8 @@ class ExchangeMixin:
                                prefix=np.zeros(pl, dtype=np.int32) if pl > 0 else None,
                                timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN),
                                temperature=temps[k], seed=seeds[k], top_k=top_k, top_p=top_p,
-                               logprobs=LP_TOP if fl & LOGPROBS else -1))
+                               logprobs=LP_TOP if fl & LOGPROBS else -1, presence_penalty=pres,
+                               frequency_penalty=freq, repetition_penalty=rep))
         return out
 
     def _owe_logprobs(self, origin: int, handle: int, r: Request) -> None:

@@ -32,7 +32,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..backend.engine import BackendEngine, Request
-from ..models.message import (Message, MessageStatus, SamplingParseError, generation_record, logprobs_from_metadata,
+from ..models.message import (PENALTY_KEYS, Message, MessageStatus, SamplingParseError, generation_record,
+                              logprobs_from_metadata, penalty_from_metadata,
                               priority_name, sampling_from_metadata, truncation_from_metadata)
 from ..parallel import planner
 from ..parallel.comm import Comm, SoloComm
@@ -452,28 +453,32 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             if len(prompt) else np.zeros(1, dtype=np.int32)
         ck = conv_key(m.conversation_id) if self.kv_residency else -1
         hist, pre = self._dialog_context(m)
-        temp, seed, top_k, top_p, logprobs = self._sampling(m)
+        temp, seed, top_k, top_p, logprobs, pens = self._sampling(m)
         return Request(req_id=m.handle, prompt=p, gen_tokens=self.gen_tokens, tier=tier, meta=m, conv=ck,
                        history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed,
-                       top_k=top_k, top_p=top_p, logprobs=logprobs)
+                       top_k=top_k, top_p=top_p, logprobs=logprobs, presence_penalty=pens[0],
+                       frequency_penalty=pens[1], repetition_penalty=pens[2])
 
     @staticmethod
-    def _sampling(m: Message) -> Tuple[float, int, int, float, int]:
+    def _sampling(m: Message) -> Tuple[float, int, int, float, int, Tuple[float, float, float]]:
         """The message's effective ``(temperature, seed, top_k, top_p,
-        logprobs)`` (``metadata.sampling``), lenient: this path also serves
+        logprobs, (presence, frequency, repetition penalty))``
+        (``metadata.sampling``), lenient: this path also serves
         messages no route validated (the native ingress), so a bad
         temperature or seed falls back to greedy, a bad ``top_k`` / ``top_p``
         turns the truncation off, a bad ``logprobs`` turns the
-        log-probabilities off (-1), and each is reported in
+        log-probabilities off (-1), a bad penalty turns that penalty off,
+        and each is reported in
         ``metadata["sampling_error"]``.  A message that asked for sampling
         gets the effective values written back, so a client can replay it:
         ``top_k`` / ``top_p`` only where they are active (with a temperature,
-        and not off) and ``logprobs`` only where the message named it, so a
+        and not off), a penalty only where it is not off (greedy or not),
+        and ``logprobs`` only where the message named it, so a
         message that named none of them keeps exactly ``{"temperature",
         "seed"}``."""
         md = m.metadata
         if not md or "sampling" not in md:
-            return 0.0, 0, 0, 1.0, -1             # greedy (the default traffic): the seed is never read
+            return 0.0, 0, 0, 1.0, -1, (0.0, 0.0, 1.0)    # greedy (the default traffic): the seed is never read
         try:
             temp, seed = sampling_from_metadata(md, m.id)
         except SamplingParseError as e:
@@ -489,6 +494,13 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         except SamplingParseError as e:
             md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
             logprobs = -1
+        pens = []
+        for key, (_lo, _hi, off) in PENALTY_KEYS.items():
+            try:
+                pens.append(penalty_from_metadata(md, key))
+            except SamplingParseError as e:
+                md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
+                pens.append(off)
         if temp <= 0:
             top_k, top_p = 0, 1.0                 # (accepted, without effect)
         eff = {"temperature": temp, "seed": seed}
@@ -498,8 +510,11 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             eff["top_p"] = top_p
         if logprobs >= 0:
             eff["logprobs"] = logprobs
+        for (key, (_lo, _hi, off)), v in zip(PENALTY_KEYS.items(), pens):
+            if v != off:
+                eff[key] = v
         md["sampling"] = eff
-        return temp, seed, top_k, top_p, logprobs
+        return temp, seed, top_k, top_p, logprobs, tuple(pens)
 
     @staticmethod
     def _attach_generation(m: Message, tokens, lp, top_ids, top_lp) -> None:

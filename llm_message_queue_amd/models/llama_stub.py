@@ -250,7 +250,7 @@ class LlamaStub:
     def forward(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 sample_idx: torch.Tensor, tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
                 small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
-                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None, logp=None):
+                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None, logp=None, pen=None):
         """One step over T tokens; returns greedy next-token ids for the rows
         in ``sample_idx`` (the last token of each request's chunk).  With
         ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
@@ -265,6 +265,16 @@ class LlamaStub:
         lp float32 [L][6], ids int32 [L][5])`` with ``ops.logprob_head``'s
         scores of the tokens finally chosen, after the truncation overwrite
         (the tokens themselves are what they are without it).
+        ``pen`` = (hist int32 [slots][max_ctx], rec int32 [Q], rows int64 [P],
+        spans int32 [P][4], params float32 [P][3], top_k int32 [P], top_p
+        float32 [P], n_greedy): the device-side token history, the token rows
+        of this forward to record in it (``ops.history_record``, before
+        anything reads it; a forward that samples nothing still records),
+        and the sampled rows that ask for a presence / frequency / repetition
+        penalty, greedy or sampling, the first ``n_greedy`` of them greedy.
+        Those rows are drawn again by ``ops.penalised_head`` with their own
+        ``top_k`` / ``top_p`` and overwrite their first draw; the caller keeps
+        them out of ``trunc``, so a row is drawn again once.
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -275,6 +285,8 @@ class LlamaStub:
         where the tiles cannot fill the partition.  ``quant`` (a model built
         with ``small_weights="fp8"``): every layer GEMM of this forward reads
         the FP8 weights (``hidden``); the head stays bf16."""
+        if pen is not None and pen[1].numel():
+            self.ops.history_record(pen[0], tokens, pos, slot, pen[1])
         if self.prune_last and self.residual_in_gemm:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus,
                               quant=quant)
@@ -292,6 +304,17 @@ class LlamaStub:
                     keys.index_select(0, rows), top_k, top_p))
         else:
             out = self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
+        if pen is not None and pen[2].numel():
+            hist, _, rows, spans, params, top_k, top_p, n_greedy = pen
+            P = rows.numel()
+            if inv_temp is not None and keys is not None:
+                it, kk = inv_temp.index_select(0, rows), keys.index_select(0, rows)
+            else:                                     # an all-greedy step: no noise is read
+                it = torch.zeros(P, dtype=torch.float32, device=out.device)
+                kk = torch.zeros((P, 2), dtype=torch.int32, device=out.device)
+            out.index_copy_(0, rows, self.ops.penalised_head(
+                sel.index_select(0, rows), self.lm_head, it, kk, top_k, top_p, hist, spans, params,
+                n_greedy=n_greedy))
         if logp is None:
             return out
         lp, ids = self.ops.logprob_head(sel.index_select(0, logp), self.lm_head, out.index_select(0, logp))

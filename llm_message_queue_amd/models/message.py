@@ -329,7 +329,8 @@ def sampling_from_metadata(md: Any, message_id: str = "") -> tuple:
 
     ``temperature``: 0 (greedy, the default) or a number in [0.05, 2.0].
     ``seed``: an integer in [0, 2^63); without one, ``default_seed(message_id)``.
-    ``top_k`` / ``top_p`` of the same object: :func:`truncation_from_metadata`.
+    ``top_k`` / ``top_p`` of the same object: :func:`truncation_from_metadata`;
+    its penalties: :func:`penalties_from_metadata`.
     Raises ``SamplingParseError`` on anything else."""
     sp = md.get("sampling") if isinstance(md, dict) else None
     if sp is None:
@@ -397,6 +398,41 @@ def logprobs_from_metadata(md: Any) -> int:
     if isinstance(n, bool) or not isinstance(n, int) or not (0 <= n <= LOGPROBS_MAX):
         raise SamplingParseError(f"sampling.logprobs must be an integer in [0, {LOGPROBS_MAX}]")
     return int(n)
+
+
+# the penalty keys of ``metadata.sampling``: (lowest, highest, the value that is off)
+PENALTY_KEYS = {"presence_penalty": (-2.0, 2.0, 0.0), "frequency_penalty": (-2.0, 2.0, 0.0),
+                "repetition_penalty": (0.5, 2.0, 1.0)}
+
+
+def penalty_from_metadata(md: Any, key: str) -> float:
+    """One of ``presence_penalty`` / ``frequency_penalty`` /
+    ``repetition_penalty`` of a message's ``metadata.sampling`` object,
+    rounded to hundredths; the key's off value where it is absent.  Raises
+    ``SamplingParseError`` on anything but a number in the key's range."""
+    lo, hi, off = PENALTY_KEYS[key]
+    sp = md.get("sampling") if isinstance(md, dict) else None
+    if sp is None:
+        return off
+    if not isinstance(sp, dict):
+        raise SamplingParseError("sampling must be an object")
+    if key not in sp:
+        return off
+    v = sp[key]
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not (lo <= v <= hi):
+        raise SamplingParseError(f"sampling.{key} must be a number in [{lo}, {hi}]")
+    return int(round(float(v) * 100.0)) / 100.0
+
+
+def penalties_from_metadata(md: Any) -> tuple:
+    """``(presence_penalty, frequency_penalty, repetition_penalty)`` of a
+    message's ``metadata.sampling`` object: numbers in [-2, 2], [-2, 2] and
+    [0.5, 2], rounded to hundredths; 0, 0 and 1.0 (the defaults) are off.
+    They work with or without a ``temperature`` and apply before it
+    (``csrc/kernels/penalty_kernels.h``): presence and frequency over the
+    tokens generated so far, repetition over those and the message's own
+    prompt.  Raises ``SamplingParseError`` on anything else."""
+    return tuple(penalty_from_metadata(md, k) for k in PENALTY_KEYS)
 
 
 def generation_record(tokens, token_logprobs, top_ids, top_logprobs, n: int) -> Dict[str, Any]:

@@ -128,7 +128,7 @@ def _scratch_entry(device, stream: int, name: str):
 
 def _scratch(device, stream: int, name: str, *specs):
     """The kernels' grow-only scratch, one entry per (device, stream) and user
-    ("split", "rms", "skinny", "head", "trunc"): the entry's tensors, one per
+    ("split", "rms", "skinny", "head", "trunc", "pen"): the entry's tensors, one per
     ``(need, floor, alloc, dtype)`` in ``specs``.  A tensor of at least
     ``need`` elements is returned as it is, so launches in stream order share
     it and concurrent streams never do.  One too small is replaced by
@@ -735,6 +735,97 @@ def token_logprobs(logits: torch.Tensor, tok: torch.Tensor, vocab: int = None, o
         _native.require_hipops().logprobs(logits.data_ptr(), R, V, ld, tok.data_ptr(), lp.data_ptr(), ids.data_ptr(),
                                           torch.cuda.current_stream(logits.device).cuda_stream)
     return lp.view(-1)[:R * (1 + LP_TOP)].view(R, 1 + LP_TOP), ids.view(-1)[:R * LP_TOP].view(R, LP_TOP)
+
+
+from .sampling import PEN_HIST_MAX  # noqa: E402  (history entries a row)
+
+
+def _pen_logits(fn: str, logits: torch.Tensor, vocab):
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or not logits.is_cuda or not logits.is_contiguous():
+        raise ValueError(f"{fn}: logits must be contiguous bfloat16 [R][ld] on a GPU")
+    R, ld = logits.shape
+    if R:
+        _check(logits, "logits")
+    V = ld if vocab is None else int(vocab)
+    if not 0 < V <= ld or ld % 8:
+        raise ValueError(f"{fn}: needs 0 < vocab <= ld and ld % 8 == 0 (vocab={V} ld={ld})")
+    return R, ld, V
+
+
+def _pen_hist(fn: str, hist: torch.Tensor, device):
+    if hist.dtype != torch.int32 or hist.dim() != 2 or not hist.is_contiguous() or hist.device != device \
+            or hist.numel() == 0 or hist.numel() >= 1 << 31:
+        raise ValueError(f"{fn}: hist must be contiguous int32 [slots][stride] on the same device")
+
+
+def penalise(logits: torch.Tensor, hist: torch.Tensor, spans: torch.Tensor, params: torch.Tensor,
+             vocab: int = None) -> torch.Tensor:
+    """Edit bf16 ``logits`` [R][ld] in place by the presence / frequency /
+    repetition penalties of their rows' token histories (``csrc/kernels/
+    penalty_kernels.h`` holds the contract, ``ops.sampling.
+    penalise_rows_reference`` is its bit-exact twin).  ``hist`` int32
+    [slots][stride <= PEN_HIST_MAX], ``spans`` int32 [>= R][4] = (slot, from,
+    split, end): row r's history is ``hist[slot][from:end]``, its first
+    ``split - from`` entries prompt tokens; ``params`` float32 [>= R][3] =
+    (presence, frequency, repetition).  ``vocab``: the columns that count
+    (default ld).  Returns ``logits``."""
+    R, ld, V = _pen_logits("penalise", logits, vocab)
+    _pen_hist("penalise", hist, logits.device)
+    if hist.shape[1] > PEN_HIST_MAX:
+        raise ValueError(f"penalise: a history of {hist.shape[1]} entries exceeds PEN_HIST_MAX = {PEN_HIST_MAX}")
+    for t, n, dt, w in ((spans, "spans", torch.int32, 4), (params, "params", torch.float32, 3)):
+        if t.dtype != dt or t.dim() != 2 or t.shape[1] != w or t.shape[0] < R or not t.is_contiguous() \
+                or t.device != logits.device:
+            raise ValueError(f"penalise: {n} must be contiguous {dt} [>= R][{w}] on the logits' device")
+    if R:
+        _native.require_hipops().penalise(logits.data_ptr(), R, V, ld, hist.data_ptr(), hist.shape[0], hist.shape[1],
+                                          spans.data_ptr(), params.data_ptr(),
+                                          torch.cuda.current_stream(logits.device).cuda_stream)
+    return logits
+
+
+def penalised_argmax(logits: torch.Tensor, vocab: int = None, inv_temp: torch.Tensor = None,
+                     out: torch.Tensor = None) -> torch.Tensor:
+    """The greedy pick over (edited) bf16 ``logits`` [R][ld] -> int32 [R]:
+    argmax over the finite columns < ``vocab``, ties to the lower column, 0
+    for a row with none (``penalty_kernels.h``; twin ``ops.sampling.
+    penalised_pick_reference``).  With ``inv_temp`` (float32 [>= R]) only the
+    rows with ``inv_temp <= 0`` are written; the others keep ``out``'s value."""
+    R, ld, V = _pen_logits("penalised_argmax", logits, vocab)
+    if inv_temp is not None and (inv_temp.dtype != torch.float32 or inv_temp.dim() != 1 or inv_temp.numel() < R
+                                 or not inv_temp.is_contiguous() or inv_temp.device != logits.device):
+        raise ValueError("penalised_argmax: inv_temp must be contiguous float32 [>= R] on the logits' device")
+    y = out if out is not None else torch.zeros(R, dtype=torch.int32, device=logits.device)
+    if y.dtype != torch.int32 or y.dim() != 1 or y.numel() < R or not y.is_contiguous() or y.device != logits.device:
+        raise ValueError("penalised_argmax: out must be contiguous int32 [>= R] on the logits' device")
+    if R:
+        _native.require_hipops().penalised_argmax(logits.data_ptr(), R, V, ld,
+                                                  inv_temp.data_ptr() if inv_temp is not None else 0, y.data_ptr(),
+                                                  torch.cuda.current_stream(logits.device).cuda_stream)
+    return y[:R]
+
+
+def history_record(hist: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
+                   rows: torch.Tensor) -> None:
+    """``hist[slot[t]][pos[t]] = tok[t]`` for the token rows ``t`` in ``rows``
+    (int32 [Q]) of a forward's ``tok`` (int64 [T]), ``pos`` and ``slot``
+    (int32 [T]): the device-side token history the penalties read
+    (``penalty_kernels.h``).  A row, slot or position out of range writes
+    nothing."""
+    if not hist.is_cuda:
+        raise ValueError("history_record: hist must be on a GPU")
+    _pen_hist("history_record", hist, hist.device)
+    T = tok.numel()
+    for t, n, dt, ln in ((tok, "tok", torch.int64, T), (pos, "pos", torch.int32, T), (slot, "slot", torch.int32, T),
+                         (rows, "rows", torch.int32, rows.numel())):
+        if t.dtype != dt or t.dim() != 1 or t.numel() != ln or not t.is_contiguous() or t.device != hist.device:
+            raise ValueError(f"history_record: {n} must be contiguous {dt}, tok / pos / slot of one length, "
+                             "on hist's device")
+    Q = rows.numel()
+    if Q and T:
+        _native.require_hipops().history_record(hist.data_ptr(), hist.shape[0], hist.shape[1], tok.data_ptr(),
+                                                pos.data_ptr(), slot.data_ptr(), T, rows.data_ptr(), Q,
+                                                torch.cuda.current_stream(hist.device).cuda_stream)
 
 
 def sample_bits(keys: torch.Tensor, n0: int, count: int) -> torch.Tensor:

@@ -151,6 +151,55 @@ class HipOps:
             lg = lg.contiguous()
         return G.token_logprobs(lg, tok.to(torch.int32).contiguous(), vocab=V)
 
+    def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None):
+        """Tokens of the LM head (int32 [R]) for the rows that ask for a
+        presence / frequency / repetition penalty.  Their logits come as
+        ``truncated_head``'s do (the tile kernel's store epilogue whatever R
+        is, ``F.linear`` for a shape it refuses), in a scratch entry of their
+        own; ``ops.gemm.penalise`` edits them in place by each row's history
+        (``hist`` int32 [slots][max_ctx], ``spans`` int32 [R][4], ``params``
+        float32 [R][3]: ``csrc/kernels/penalty_kernels.h``).  Then a row with
+        ``inv_temp > 0`` is drawn by ``ops.gemm.sample_truncated`` under its
+        ``top_k`` / ``top_p`` (0 / 1.0: none) and a greedy row picked by
+        ``ops.gemm.penalised_argmax``; the sampler never sees a greedy row
+        (its contract wants ``inv_temp > 0``).  ``n_greedy``: the rows come
+        greedy first, so many of them (the engine lists them so).  Without
+        it the rows are partitioned here, which reads ``inv_temp`` back on
+        the host (a synchronisation)."""
+        from . import gemm as G
+        R, V = x.shape[0], w.shape[0]
+        order = None
+        if n_greedy is None:
+            hot = inv_temp[:R] > 0
+            n_greedy = R - int(hot.sum())
+            if 0 < n_greedy < R:
+                order = torch.argsort(hot.to(torch.uint8), stable=True)
+                x, inv_temp, keys, top_k, top_p, spans, params = (
+                    t[:R].index_select(0, order) for t in (x, inv_temp, keys, top_k, top_p, spans, params))
+        if G.supported(R, V, x.shape[1]):
+            buf, = G._scratch(x.device, _stream(x), "pen", (R * V, 0, torch.empty, torch.bfloat16))
+            lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
+        else:
+            lg = torch.nn.functional.linear(x, w)
+            if V % 8:
+                lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
+            lg = lg.contiguous()
+        G.penalise(lg, hist, spans.contiguous(), params.contiguous(), vocab=V)
+        g = min(max(int(n_greedy), 0), R)
+        out = torch.zeros(R, dtype=torch.int32, device=x.device)
+        if g < R:
+            G.sample_truncated(lg[g:], inv_temp.contiguous()[g:], keys.contiguous()[g:], top_k.contiguous()[g:],
+                               top_p.contiguous()[g:], vocab=V, out=out[g:])
+        if g:
+            G.penalised_argmax(lg[:g], vocab=V, out=out)
+        return out if order is None else torch.empty_like(out).index_copy_(0, order, out)
+
+    def history_record(self, hist, tok, pos, slot, rows):
+        """Record the token rows ``rows`` of a forward in the device-side
+        token history (``ops.gemm.history_record``)."""
+        from . import gemm as G
+        G.history_record(hist, tok.contiguous(), pos.contiguous(), slot.contiguous(), rows.contiguous())
+
     def mlp_up(self, x: torch.Tensor, w_gu: torch.Tensor, fused: bool, min_fused_tokens: int) -> torch.Tensor:
         """silu(x·Wgᵀ) * (x·Wuᵀ).  ``fused``: ``w_gu`` is in swiglu order and
         steps of >= ``min_fused_tokens`` rows run the hand-written GEMM with
@@ -322,6 +371,31 @@ class RefOps:
         lp, ids = logprob_reference(lg, tok.cpu().numpy())
         return (torch.from_numpy(lp.astype("float32")).to(x.device),
                 torch.from_numpy(ids.astype("int32")).to(x.device))
+
+    def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None):
+        """Reference of ``HipOps.penalised_head``: fp32 logits rounded to bf16,
+        the numpy twin of the edit (``ops.sampling.penalise_rows_reference``),
+        then ``sample_truncated_reference`` for a row with ``inv_temp > 0``
+        and ``penalised_pick_reference`` for a greedy one."""
+        from .sampling import (bf16_values, penalise_rows_reference, penalised_pick_reference,
+                               sample_truncated_reference)
+        R, V = x.shape[0], w.shape[0]
+        lg = (x.float() @ w.float().t()).to(torch.bfloat16).cpu().contiguous()
+        bits = penalise_rows_reference(lg.view(torch.int16).numpy().view("uint16"), V, hist.cpu().numpy(),
+                                       spans[:R].cpu().numpy(), params[:R].cpu().numpy())
+        it = inv_temp[:R].cpu().numpy()
+        picks = penalised_pick_reference(bits, V)
+        hot = it > 0
+        if hot.any():
+            kk = keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
+            picks[hot] = sample_truncated_reference(bf16_values(bits)[hot], it[hot], kk[hot],
+                                                    top_k[:R].cpu().numpy()[hot], top_p[:R].cpu().numpy()[hot])
+        return torch.from_numpy(picks).to(x.device)
+
+    def history_record(self, hist, tok, pos, slot, rows):
+        """Reference of ``HipOps.history_record``."""
+        r = rows.long()
+        hist[slot.long()[r], pos.long()[r]] = tok[r].to(hist.dtype)
 
     def mlp_up(self, x, w_gu, fused: bool, min_fused_tokens: int):
         """Reference of ``HipOps.mlp_up`` (``w_gu`` in swiglu order if fused)."""

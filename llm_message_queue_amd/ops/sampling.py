@@ -15,8 +15,15 @@ over whole groups of equal bf16 logits, then the same draw over what is kept).
 Log-probabilities: :func:`logprob_reference` is the float64 twin of
 ``csrc/kernels/logprob_kernels.h`` and :func:`logprob_bound` the bound on the
 device's distance from it, derived there.
+
+Penalties: :func:`penalise_reference` is the bit-exact twin of the edit in
+``csrc/kernels/penalty_kernels.h`` (over bf16 bit patterns, so padding and
+non-finite values compare too), :func:`penalised_pick_reference` that of its
+greedy pick.
 """
 from __future__ import annotations
+
+from fractions import Fraction
 
 import numpy as np
 
@@ -211,3 +218,109 @@ def sample_reference(logits, inv_temp, keys) -> np.ndarray:
         sc = np.where(it[i:j, None] != 0, lg[i:j] * it[i:j, None] + g, lg[i:j])
         out[i:j] = sc.argmax(axis=1)
     return out
+
+
+# history entries a row: the package's one copy of csrc/kernels/penalty_kernels.h's PEN_HIST_MAX (the engine
+# checks its max_ctx against it)
+PEN_HIST_MAX = 4096
+
+
+def bf16_bits(x) -> np.ndarray:
+    """float32 values -> bf16 bit patterns (uint16), round to nearest even; a
+    NaN becomes 0x7fc0, an overflow an infinity (``pen_bf16``)."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = ((u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)).astype(np.uint16)
+    return np.where((u & np.uint64(0x7FFFFFFF)) > np.uint64(0x7F800000), np.uint16(0x7FC0), r)
+
+
+def bf16_values(bits) -> np.ndarray:
+    """bf16 bit patterns (uint16) -> their float32 values."""
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def _f32_nearest_even(q) -> np.float32:
+    """The float32 nearest to the non-zero rational ``q``, ties to even
+    (denormals and overflow included)."""
+    neg, a = q < 0, abs(q)
+    e = a.numerator.bit_length() - a.denominator.bit_length()
+    if a < Fraction(2) ** e:
+        e -= 1                                       # 2^e <= a < 2^(e + 1)
+    ulp = Fraction(2) ** (max(e, -126) - 23)
+    m, rem = divmod(a, ulp)
+    m = int(m)
+    if rem * 2 > ulp or (rem * 2 == ulp and (m & 1)):
+        m += 1
+    v = float(m * ulp)                               # (exact in float64; above the float32 range it becomes inf)
+    with np.errstate(over="ignore"):
+        return np.float32(-v if neg else v)
+
+
+def _fma_f32(a: np.float32, c: int, x: np.float32) -> np.float32:
+    """``fma(a, float(c), x)`` in float32 with one rounding (``a`` finite,
+    ``c`` a small non-negative integer)."""
+    if not np.isfinite(x):
+        return x
+    q = Fraction(float(a)) * int(c) + Fraction(float(x))
+    if q != 0:
+        return _f32_nearest_even(q)
+    p_neg = bool(np.signbit(a))                      # (the product's sign: c >= 0)
+    both_zero = (float(a) == 0.0 or int(c) == 0) and float(x) == 0.0
+    return np.float32(-0.0) if (both_zero and p_neg and np.signbit(x)) else np.float32(0.0)
+
+
+def penalise_reference(bits, vocab: int, h, n_p: int, pp, fp, rp) -> np.ndarray:
+    """The twin of the edit in ``csrc/kernels/penalty_kernels.h``, which holds
+    the contract, bit for bit: one row of bf16 bit patterns ``bits`` (uint16
+    [ld], columns ``vocab .. ld`` padding) under the history ``h`` (ids, the
+    first ``n_p`` prompt tokens, the rest generated) and the float32
+    parameters; returns the edited copy.  Per distinct id in [0, vocab):
+    ``x = x > 0 ? x / rp : x * rp`` if ``rp != 1``, ``x = fma(-fp, c_gen,
+    x)``, ``x -= pp`` if ``c_gen > 0``, each rounded once in float32, then
+    bf16 by round-to-nearest-even."""
+    out = np.array(bits, dtype=np.uint16).reshape(-1)
+    h = np.asarray(h, dtype=np.int64).reshape(-1)
+    pp, fp, rp = np.float32(pp), np.float32(fp), np.float32(rp)
+    n_p = min(max(int(n_p), 0), len(h))
+    with np.errstate(all="ignore"):
+        for t in np.unique(h):
+            if not 0 <= t < int(vocab):
+                continue
+            c_gen = int(np.count_nonzero(h[n_p:] == t))
+            x = bf16_values(out[t:t + 1])[0]
+            if rp != np.float32(1.0):
+                x = np.float32(x / rp) if x > 0 else np.float32(x * rp)
+            x = _fma_f32(-fp, c_gen, x)
+            if c_gen > 0:
+                x = np.float32(x - pp)
+            out[t] = bf16_bits(np.array([x], dtype=np.float32))[0]
+    return out
+
+
+def penalise_rows_reference(bits, vocab: int, hist, spans, params) -> np.ndarray:
+    """:func:`penalise_reference` over rows [R][ld] the way the device reads
+    its histories: ``hist`` int32 [slots][stride], ``spans`` [R][4] = (slot,
+    from, split, end), ``params`` float32 [R][3] = (pp, fp, rp); spans are
+    clamped to the table as the kernel clamps them."""
+    out = np.array(bits, dtype=np.uint16)
+    hist = np.asarray(hist)
+    stride = hist.shape[1]
+    spans = np.asarray(spans, dtype=np.int64).reshape(-1, 4)
+    params = np.asarray(params, dtype=np.float32).reshape(-1, 3)
+    for r in range(out.shape[0]):
+        s, a, m, b = (int(v) for v in spans[r])
+        if not 0 <= s < hist.shape[0]:
+            continue
+        a = min(max(a, 0), stride)
+        b = min(min(max(b, a), stride), a + min(stride, PEN_HIST_MAX))
+        m = min(max(m, a), b)
+        out[r] = penalise_reference(out[r], vocab, hist[s, a:b], m - a, *params[r])
+    return out
+
+
+def penalised_pick_reference(bits, vocab: int) -> np.ndarray:
+    """The twin of ``penalised_argmax_kernel``: int32 [R], per row of bf16 bit
+    patterns [R][ld] the argmax over the finite columns < ``vocab``, ties to
+    the lower column, 0 for a row with none."""
+    v = bf16_values(np.asarray(bits, dtype=np.uint16).reshape(len(bits), -1)[:, :int(vocab)]).astype(np.float64)
+    v = np.where(np.isfinite(v), v, -np.inf)
+    return np.where(np.isfinite(v.max(axis=1)), v.argmax(axis=1), 0).astype(np.int32)

@@ -19,6 +19,7 @@
 #include "gemm_kernels.h"
 #include "kv_migrate_kernels.h"
 #include "llama_kernels.h"
+#include "logit_edit_kernels.h"
 #include "logprob_kernels.h"
 #include "penalty_kernels.h"
 #include "sample_truncate_kernels.h"
@@ -394,15 +395,17 @@ static void sample_bits(uintptr_t keys, int n_keys, uint32_t n0, int count, uint
   check_launch();
 }
 
-// out[r] = the top-k / top-p truncated draw of row r of bf16 logits [R][ld] (columns < V):
-// sample_truncate_kernels.h holds the contract.  One block a row, grid-stride above ST_MAX_BLOCKS.
+// out[r] = the top-k / top-p / min-p truncated draw of row r of bf16 logits [R][ld] (columns < V):
+// sample_truncate_kernels.h holds the contract.  log_min_p 0: no min-p.  One block a row, grid-stride above
+// ST_MAX_BLOCKS.
 static void sample_truncated(uintptr_t logits, int R, int V, int ld, uintptr_t inv_temp, uintptr_t keys,
-                             uintptr_t top_k, uintptr_t top_p, uintptr_t out, uintptr_t stream) {
+                             uintptr_t top_k, uintptr_t top_p, uintptr_t out, uintptr_t stream, uintptr_t log_min_p) {
   const char* fn = "sample_truncated";
   require_in(fn, R >= 0 && V > 0 && ld >= V && ld % 8 == 0, "needs R >= 0, 0 < V <= ld, ld % 8 == 0");
   require_in(fn, logits != 0 && logits % 16 == 0, "logits must be 16-byte aligned");
   require_in(fn, inv_temp != 0 && keys != 0 && top_k != 0 && top_p != 0 && out != 0, "null pointer");
-  require_in(fn, inv_temp % 4 == 0 && keys % 4 == 0 && top_k % 4 == 0 && top_p % 4 == 0 && out % 4 == 0,
+  require_in(fn, inv_temp % 4 == 0 && keys % 4 == 0 && top_k % 4 == 0 && top_p % 4 == 0 && out % 4 == 0 &&
+                     log_min_p % 4 == 0,
              "per-row arrays must be 4-byte aligned");
   if (R == 0) return;
   static bool attr = false;
@@ -413,7 +416,8 @@ static void sample_truncated(uintptr_t logits, int R, int V, int ld, uintptr_t i
   }
   hipLaunchKernelGGL(sample_truncated_kernel, dim3(std::min(R, (int)ST_MAX_BLOCKS)), dim3(ST_THREADS), ST_LDS_BYTES,
                      S(stream), P<const uint16_t>(logits), R, V, ld, P<const float>(inv_temp),
-                     P<const uint32_t>(keys), P<const int32_t>(top_k), P<const float>(top_p), P<int32_t>(out));
+                     P<const uint32_t>(keys), P<const int32_t>(top_k), P<const float>(top_p), P<const float>(log_min_p),
+                     P<int32_t>(out));
   check_launch();
 }
 
@@ -431,6 +435,24 @@ static void logprobs(uintptr_t logits, int R, int V, int ld, uintptr_t tok, uint
   hipLaunchKernelGGL(logprob_kernel, dim3(std::min(R, (int)LP_MAX_BLOCKS)), dim3(LP_THREADS), 0, S(stream),
                      P<const uint16_t>(logits), R, V, ld, P<const int32_t>(tok), P<float>(out_lp),
                      P<int32_t>(out_id));
+  check_launch();
+}
+
+// Edit rows of bf16 logits [R][ld] (columns < V) in place by their allow lists and additive biases:
+// logit_edit_kernels.h holds the contract.  ids int32 [N] and vals fp32 [N] are the flat lists, spans int32 [R][4] =
+// (allow_off, n_allow, bias_off, n_bias) name a row's parts of them.  One block a row, grid-stride above
+// LE_MAX_BLOCKS.
+static void logit_edit(uintptr_t logits, int R, int V, int ld, uintptr_t ids, uintptr_t vals, int N, uintptr_t spans,
+                       uintptr_t stream) {
+  const char* fn = "logit_edit";
+  require_in(fn, R >= 0 && V > 0 && ld >= V && ld % 8 == 0 && N >= 0, "needs R, N >= 0, 0 < V <= ld, ld % 8 == 0");
+  require_in(fn, logits != 0 && logits % 16 == 0, "logits must be 16-byte aligned");
+  require_in(fn, spans != 0 && (N == 0 || (ids != 0 && vals != 0)), "null pointer");
+  require_in(fn, ids % 4 == 0 && vals % 4 == 0 && spans % 4 == 0, "arrays must be 4-byte aligned");
+  if (R == 0 || N == 0) return;
+  hipLaunchKernelGGL(logit_edit_kernel, dim3(std::min(R, (int)LE_MAX_BLOCKS)), dim3(LE_THREADS), 0, S(stream),
+                     P<uint16_t>(logits), R, V, ld, P<const int32_t>(ids), P<const float>(vals), N,
+                     P<const int32_t>(spans));
   check_launch();
 }
 
@@ -812,7 +834,8 @@ PYBIND11_MODULE(_hipops, m) {
   m.def("sample_bits", &sample_bits, py::arg("keys"), py::arg("n_keys"), py::arg("n0"), py::arg("count"),
         py::arg("out"), py::arg("stream"));
   m.def("sample_truncated", &sample_truncated, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"),
-        py::arg("inv_temp"), py::arg("keys"), py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("stream"));
+        py::arg("inv_temp"), py::arg("keys"), py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("stream"),
+        py::arg("log_min_p") = 0);
   m.def("logprobs", &logprobs, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"), py::arg("tok"),
         py::arg("out_lp"), py::arg("out_id"), py::arg("stream"));
   m.attr("LP_TOP") = (int)LP_TOP;
@@ -825,6 +848,10 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("pos"), py::arg("slot"), py::arg("T"), py::arg("rows"), py::arg("Q"), py::arg("stream"));
   m.attr("PEN_HIST_MAX") = (int)PEN_HIST_MAX;
   m.attr("PEN_MAX_BLOCKS") = (int)PEN_MAX_BLOCKS;
+  m.def("logit_edit", &logit_edit, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"), py::arg("ids"),
+        py::arg("vals"), py::arg("N"), py::arg("spans"), py::arg("stream"));
+  m.attr("LE_MAX") = (int)LE_MAX;
+  m.attr("LE_MAX_BLOCKS") = (int)LE_MAX_BLOCKS;
   m.def("row_rms", &row_rms);
   m.attr("GEMM_EPI_STORE") = (int)GM_EPI_STORE;
   m.attr("GEMM_EPI_SWIGLU") = (int)GM_EPI_SWIGLU;

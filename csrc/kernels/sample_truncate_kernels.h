@@ -1,5 +1,5 @@
-// Top-k / top-p (nucleus) sampling over a row of bf16 logits: the selection
-// and the draw in one kernel, under the noise contract of sample_noise.h.
+// Top-k / top-p (nucleus) / min-p sampling over a row of bf16 logits: the
+// selection and the draw in one kernel, under the noise contract of sample_noise.h.
 // Rows that ask for truncation take this path (logits from the store-epilogue
 // GEMM); every other row keeps the fused LM head (GM_EPI_SAMPLE), which needs
 // no logits tensor but cannot know a per-row threshold in its single pass.
@@ -8,8 +8,9 @@
 // sample_truncated_reference are the numpy twin, in float64):
 //
 //   inputs     bf16 logits l[0..V), inv_temp (fp32, > 0), the row key (k0, k1),
-//              top_k (int, 0 = off), top_p (fp32, >= 1 = off)
-//   order      temperature, then top-k, then top-p, then the draw
+//              top_k (int, 0 = off), top_p (fp32, >= 1 = off), log_min_p (fp32,
+//              the host's float32(log(min_p)); -inf, or no array at all = off)
+//   order      temperature, then top-k, then top-p, then min-p, then the draw
 //   candidates the columns with a finite logit.  A NaN (or infinite) logit is
 //              never kept; a row with no finite logit yields token 0
 //   groups     selection works on values, not positions: the distinct values
@@ -23,7 +24,17 @@
 //              inv_temp); keep the shortest prefix whose cumulative mass is >=
 //              top_p * (total mass of the groups top-k kept): a group is kept
 //              iff the mass of all groups before it is < that target
-//   first      the first group (the maximum) is always kept
+//   min-p      over what top-k and top-p kept: a column of value v is kept
+//              iff fl(fl(v - max) * inv_temp) >= log_min_p, each operation
+//              rounded once in fp32 (__fsub_rn, __fmul_rn; the twin does the
+//              same in np.float32, so the rule is exact for any input).  The
+//              maximum passes every earlier rule, so this is a pure threshold
+//              on values and commutes with renormalisation; log_min_p = 0
+//              (min_p = 1) keeps exactly the group of the maximum.  Off, the
+//              test is not evaluated and the results are what they are without
+//              the argument
+//   first      the first group (the maximum) is always kept by top-k and
+//              top-p (and by min-p for any log_min_p <= 0)
 //   pick       argmax over kept columns n of float(l[n]) * inv_temp +
 //              G(k0, k1, n), G the Gumbel of sample_noise.h; ties to the lower
 //              column: an exact draw from the renormalised truncated softmax
@@ -47,8 +58,9 @@
 //      First the top-k threshold key and the kept mass, then the top-p
 //      threshold key;
 //   4. one pass that evaluates the noise for kept columns only (key >=
-//      threshold) and reduces the argmax.
-// A row without truncation (top_k == 0, top_p >= 1) skips 2 and 3.
+//      threshold, and the min-p test) and reduces the argmax.
+// A row without top-k / top-p (top_k == 0, top_p >= 1) skips 2 and 3, with or
+// without min-p.
 // Thread t's 128 counters are 129 dwords apart (one pad dword a chunk), so the
 // 64 lanes of a wave walk 64 different banks.  Counters are 32 bits: a row of
 // any length whose columns share one value cannot overflow them.
@@ -167,7 +179,7 @@ __global__ void __launch_bounds__(ST_THREADS)
 sample_truncated_kernel(const uint16_t* __restrict__ logits, int R, int V, int ld,
                         const float* __restrict__ inv_temp, const uint32_t* __restrict__ keys,
                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
-                        int32_t* __restrict__ out) {
+                        const float* __restrict__ log_min_p, int32_t* __restrict__ out) {
   extern __shared__ __align__(16) uint32_t st_lds[];
   uint32_t* hist = st_lds;
   uint32_t* part_c = st_lds + ST_HIST;
@@ -182,6 +194,8 @@ sample_truncated_kernel(const uint16_t* __restrict__ logits, int R, int V, int l
     const uint32_t k0 = keys[2 * r], k1 = keys[2 * r + 1];
     const int tk = top_k[r];
     const float tp = top_p[r];
+    const float lmp = log_min_p != nullptr ? log_min_p[r] : -INFINITY;
+    const bool by_m = !(lmp == -INFINITY);
 
     // 1. the largest candidate key
     float fmx = -INFINITY;                           // (a candidate is finite: -inf is "none")
@@ -287,7 +301,7 @@ sample_truncated_kernel(const uint16_t* __restrict__ logits, int R, int V, int l
     int bc = 0x7fffffff;
     st_row(row, V, [&](uint32_t b, int n) {
       const int k = st_key(b);
-      if (k >= thr && k >= 0) {
+      if (k >= thr && k >= 0 && (!by_m || __fmul_rn(__fsub_rn(__uint_as_float(b << 16), vmax), it) >= lmp)) {
         const float s = __uint_as_float(b << 16) * it + sn_gumbel(k0, k1, (uint32_t)n);
         if (s > bv) {                                // (columns ascend within a thread: a tie keeps the lower)
           bv = s;

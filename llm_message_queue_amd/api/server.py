@@ -36,7 +36,8 @@ from fastapi.responses import JSONResponse, Response
 
 from ..balancer.load_balancer import Endpoint, LoadBalancerError
 from ..models.message import (ConversationNotFound, Message, MessageStatus,
-                              PriorityParseError, format_time, level_priority_from_name, logprobs_from_metadata,
+                              PriorityParseError, eligibility_from_metadata, format_time,
+                              level_priority_from_name, logprobs_from_metadata,
                               parse_priority, penalties_from_metadata, priority_name, sampling_from_metadata,
                               truncation_from_metadata)
 from ..scheduler.resource_scheduler import Resource, ResourceError
@@ -255,6 +256,7 @@ def create_app(gw_app, allowed_origins: Optional[List[str]] = None,
             truncation_from_metadata(m.metadata)
             logprobs_from_metadata(m.metadata)
             penalties_from_metadata(m.metadata)
+            eligibility_from_metadata(m.metadata)
         except (ValueError, PriorityParseError, TypeError) as e:
             return _err(400, f"Invalid message format: {e}")
         bad = await _enqueue(m)

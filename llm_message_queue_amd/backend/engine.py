@@ -33,14 +33,14 @@ import collections
 import math
 import time
 from dataclasses import dataclass
-from typing import Deque, Dict, List, Optional, Sequence
+from typing import Deque, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ..models.llama_stub import LlamaConfig, LlamaStub
 from ..ops.gemm import SKINNY_CHUNKED_MAX_M, row_scale_len
-from ..ops.sampling import LP_TOP, PEN_HIST_MAX, inv_temperature, row_keys
+from ..ops.sampling import LE_MAX, LP_TOP, PEN_HIST_MAX, inv_temperature, min_p_log, row_keys
 
 
 @dataclass
@@ -101,6 +101,15 @@ class Request:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     repetition_penalty: float = 1.0
+    # which tokens are eligible.  ``allowed`` (int32 ids, at most 64) and
+    # ``logit_bias`` (int32 ids, float32 values, at most 64) edit the logits
+    # after the penalties and before the temperature, greedy or sampling
+    # (``csrc/kernels/logit_edit_kernels.h``); an id outside the vocabulary is
+    # ignored.  ``min_p`` (0: off) is one more truncation rule of a sampling
+    # request, after ``top_p``; a greedy request ignores it
+    min_p: float = 0.0
+    logit_bias: Optional[Tuple[np.ndarray, np.ndarray]] = None
+    allowed: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -341,6 +350,17 @@ class BackendEngine:
         self.s_pfrom = np.zeros(n_all, dtype=np.int64)
         self.penalised_steps = 0                            # forwards that drew a penalised row (``penalised_head``)
         self.d_hist = None                                  # the device-side token history (first penalised request)
+        # allow-lists and logit biases (``logit_edit_kernels.h``): the slot's
+        # lists, host side (allocated with the first request that has one):
+        # ``h_eids[s]`` = allow ids then bias ids, ``h_evals[s]`` the bias
+        # values at the bias ids' places, ``s_ecnt[s]`` = (n_allow, n_bias).
+        # ``s_minp``: float32 log(min_p) of a sampling slot (-inf: off)
+        self.s_edit = np.zeros(n_all, dtype=bool)
+        self.s_ecnt = np.zeros((n_all, 2), dtype=np.int32)
+        self.h_eids = self.h_evals = None
+        self.s_minp = np.full(n_all, -np.inf, dtype=np.float32)
+        self._eligibility_seen = False                      # a request has named min_p, an allow-list or a bias
+        self.edited_steps = 0                               # forwards that edited a row by such a list (``logit_edit``)
         # host copy of every scored token's log-probability and alternatives,
         # per slot, next to ``h_tokens`` (allocated with the first request that asks)
         self.h_lp = self.h_top_ids = self.h_top_lp = None
@@ -384,8 +404,9 @@ class BackendEngine:
         # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles,
         #  row index, top_k and top_p of its truncating rows, and the row index of a step's
         #  log-probability rows, and a penalised step's block: 10 words per penalised row and the token
-        #  rows to record)
-        self._pins = [self._alloc_pin(4 * (8 * self.token_budget + 16 * slots + 64 + 3 * row_scale_len(slots) + 4))
+        #  rows to record, and an edited step's block: 6 words per row and its two lists, ids and values)
+        self._pins = [self._alloc_pin(4 * (8 * self.token_budget + (22 + 4 * LE_MAX) * slots + 64
+                                           + 3 * row_scale_len(slots) + 4))
                       for _ in range(ring)]
         # sampled token ids copied back behind each forward (read at reap)
         self._out_pins = [self._alloc_pin(4 * self.n_all).view(torch.int32) for _ in range(ring)]
@@ -408,7 +429,8 @@ class BackendEngine:
             # so it never grows (a grown pinned buffer frees the old one
             # behind the copies still queued from it)
             self._pins_m = [self._alloc_pin(4 * (12 * self.micro_budget + 2 * self.micro_slots + 64
-                                                 + 3 * row_scale_len(self.micro_slots) + 14 * self.micro_slots + 4))
+                                                 + 3 * row_scale_len(self.micro_slots)
+                                                 + (20 + 4 * LE_MAX) * self.micro_slots + 4))
                             for _ in range(mr)]
             self._out_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32) for _ in range(mr)]
             self._lp_pins_m = [self._alloc_lp_pin(self.micro_slots) for _ in range(mr)]
@@ -689,6 +711,40 @@ class BackendEngine:
                     self.s_penp[s] = pv
                     self.s_pen[s] = bool(pv[0] != 0 or pv[1] != 0 or pv[2] != 1)
                     self.s_pfrom[s] = base + n - n_own
+            # min_p: a sampling slot only; a value that rounds to 0 permille is off
+            # (nothing to reset before the first request that names one of the three)
+            named = bool(r.min_p) or r.allowed is not None or r.logit_bias is not None
+            if named:
+                self._eligibility_seen = True
+            if self._eligibility_seen:
+                self.s_minp[s] = -np.inf
+                self.s_edit[s] = False
+            if on and r.min_p:
+                mp = float(r.min_p)
+                if math.isfinite(mp) and 0.0 < mp <= 1.0:
+                    self.s_minp[s] = min_p_log(mp)
+            # allow-list and logit bias, greedy slots too: at most LE_MAX
+            # entries each, ids that fit an int32 (any other id is outside
+            # every vocabulary), finite non-zero bias values
+            if named and (r.allowed is not None or r.logit_bias is not None) and self.runs_model:
+                al = np.asarray(r.allowed if r.allowed is not None else (), dtype=np.int64).reshape(-1)[:LE_MAX]
+                bi, bv = r.logit_bias if r.logit_bias is not None else ((), ())
+                bi = np.asarray(bi, dtype=np.int64).reshape(-1)
+                bv = np.asarray(bv, dtype=np.float32).reshape(-1)[:len(bi)]
+                ok = np.isfinite(bv) & (bv != 0)
+                bi, bv = bi[:len(bv)][ok][:LE_MAX], bv[ok][:LE_MAX]
+                na, nb = len(al), len(bi)
+                if na or nb:
+                    if self.h_eids is None:
+                        self.h_eids = np.zeros((self.n_all, 2 * LE_MAX), dtype=np.int32)
+                        self.h_evals = np.zeros((self.n_all, 2 * LE_MAX), dtype=np.float32)
+                    i32 = lambda v: np.where((v >= 0) & (v < 1 << 31), v, -1).astype(np.int32)   # noqa: E731
+                    self.h_eids[s, :na] = i32(al)
+                    self.h_eids[s, na:na + nb] = i32(bi)
+                    self.h_evals[s, :na] = 0
+                    self.h_evals[s, na:na + nb] = bv
+                    self.s_ecnt[s] = (na, nb)
+                    self.s_edit[s] = True
             if self.s_pen[s] and self.d_hist is None:
                 # the device-side token history, indexed [slot][absolute
                 # position] (``penalty_kernels.h``).  Not filled: a fill would
@@ -1123,7 +1179,15 @@ class BackendEngine:
         # micro pool as well.  A row that also truncates leaves ``trunc``
         qrows = np.flatnonzero(self.s_pen[slot]) if self.d_hist is not None else np.zeros(0, dtype=np.int64)
         Q = len(qrows)
-        prows = np.flatnonzero(self.s_pen[samp_slots]) if (Q and S) else np.zeros(0, dtype=np.int64)
+        # Slots with an allow-list or a logit bias take the same path, their
+        # penalty off (a span whose slot is -1: no history is read, and none
+        # is recorded for them)
+        if self.h_eids is not None and S:
+            edit = self.s_edit[samp_slots]
+            prows = np.flatnonzero(edit | self.s_pen[samp_slots] if Q else edit)
+        else:
+            edit = None
+            prows = np.flatnonzero(self.s_pen[samp_slots]) if (Q and S) else np.zeros(0, dtype=np.int64)
         P = len(prows)
         n_greedy = 0
         if P:
@@ -1131,7 +1195,7 @@ class BackendEngine:
             n_greedy = int(P - hot.sum())
             prows = np.concatenate([prows[~hot], prows[hot]])
         if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling and not L \
-                and not Q:
+                and not Q and not P:
             Tb = next((b for b in self.MICRO_GRAPH_BUCKETS if b >= T and b in self._mg), 0)
             if Tb:
                 return self._launch_micro_graph(Tb, t0, t_mono, pos, slot, samp_slots, dec_src)
@@ -1144,25 +1208,61 @@ class BackendEngine:
         Sp = row_scale_len(S) if sampling else 0
         # rows that also ask for top-k / top-p: their indices into the sampled
         # rows, top_k and top_p (float32 bits) behind the keys, same copy
-        trows = np.flatnonzero((temp > 0) & ((self.s_topk[samp_slots] > 0) | (self.s_topp[samp_slots] < 1))
-                               & ~self.s_pen[samp_slots]) if sampling else ()
+        # (and, where one of them asks for min_p, every such row's log(min_p) behind them)
+        if sampling:
+            minp = self.s_minp[samp_slots]
+            by_m = minp > -np.inf
+            keep = ~self.s_pen[samp_slots] if edit is None else ~(self.s_pen[samp_slots] | edit)
+            trows = np.flatnonzero((temp > 0) & ((self.s_topk[samp_slots] > 0) | (self.s_topp[samp_slots] < 1) | by_m)
+                                   & keep)
+        else:
+            trows = ()
         R = len(trows)
+        RM = R if (R and by_m[trows].any()) else 0
         o_trn = o_smp + 3 * Sp
         # the log-probability rows behind the truncation block (nothing when
         # there are none: the buffer is then what it is without the feature)
-        o_lgp = o_trn + 3 * R
+        o_lgp = o_trn + 3 * R + RM
         # the penalty block behind the log-probability rows (empty when
         # unused): per penalised row its index, span (slot, from, split, end),
         # parameters, top_k and top_p, then the token rows to record
         o_pen = o_lgp + L
-        buf = np.empty(o_pen + 10 * P + Q, dtype=np.int32)
-        if Q:
-            buf[o_pen + 10 * P:] = qrows
+        # the edit block behind that (empty unless a row of this step has an
+        # allow-list, a bias or, penalised, a min_p): per row log(min_p) and
+        # the span (allow_off, n_allow, bias_off, n_bias), then the N ids and
+        # the N values of the rows' lists
+        o_edt = o_pen + 10 * P + Q
+        E = N = 0
         if P:
             ps = samp_slots[prows]
+            pm = self.s_minp[ps]
+            if edit is not None and edit[prows].any():
+                ec = np.where(self.s_edit[ps][:, None], self.s_ecnt[ps], 0)
+                en = ec.sum(axis=1)
+                N = int(en.sum())
+            E = P if (N or (pm > -np.inf).any()) else 0
+        buf = np.empty(o_edt + 5 * E + 2 * N, dtype=np.int32)
+        if Q:
+            buf[o_pen + 10 * P:o_edt] = qrows
+        if E:
+            buf[o_edt:o_edt + E] = pm.view(np.int32)
+            es = buf[o_edt + E:o_edt + 5 * E].reshape(E, 4)
+            es[:] = 0
+            if N:
+                off = np.cumsum(en) - en
+                es[:, 0] = off
+                es[:, 1] = ec[:, 0]
+                es[:, 2] = off + ec[:, 0]
+                es[:, 3] = ec[:, 1]
+                o_ids = o_edt + 5 * E
+                for i in np.flatnonzero(en):
+                    a, n = o_ids + int(off[i]), int(en[i])
+                    buf[a:a + n] = self.h_eids[ps[i], :n]
+                    buf[a + N:a + N + n] = self.h_evals[ps[i], :n].view(np.int32)
+        if P:
             buf[o_pen:o_pen + P] = prows
             sp = buf[o_pen + P:o_pen + 5 * P].reshape(P, 4)
-            sp[:, 0] = ps
+            sp[:, 0] = np.where(self.s_pen[ps], ps, -1)
             sp[:, 1] = self.s_pfrom[ps]
             sp[:, 2] = self.s_plen[ps]
             sp[:, 3] = self.s_plen[ps] + self.s_gen[ps]
@@ -1172,7 +1272,9 @@ class BackendEngine:
         if R:
             buf[o_trn:o_trn + R] = trows
             buf[o_trn + R:o_trn + 2 * R] = self.s_topk[samp_slots[trows]]
-            buf[o_trn + 2 * R:o_lgp] = self.s_topp[samp_slots[trows]].view(np.int32)
+            buf[o_trn + 2 * R:o_trn + 3 * R] = self.s_topp[samp_slots[trows]].view(np.int32)
+            if RM:
+                buf[o_trn + 3 * R:o_lgp] = minp[trows].view(np.int32)
         if L:
             buf[o_lgp:o_pen] = lrows
         if sampling:
@@ -1218,16 +1320,24 @@ class BackendEngine:
                 if R:
                     skw["trunc"] = (d[o_trn:o_trn + R].long(), d[o_trn + R:o_trn + 2 * R],
                                     d[o_trn + 2 * R:o_trn + 3 * R].view(torch.float32))
+                    if RM:
+                        skw["trunc"] += (d[o_trn + 3 * R:o_lgp].view(torch.float32),)
                     self.truncated_steps += 1
             if L:
                 skw["logp"] = d[o_lgp:o_lgp + L].long()
                 self.logprob_steps += 1
-            if Q:
+            if Q or P:
                 skw["pen"] = (self.d_hist, d[o_pen + 10 * P:o_pen + 10 * P + Q], d[o_pen:o_pen + P].long(),
                               d[o_pen + P:o_pen + 5 * P].view(P, 4),
                               d[o_pen + 5 * P:o_pen + 8 * P].view(torch.float32).view(P, 3),
                               d[o_pen + 8 * P:o_pen + 9 * P], d[o_pen + 9 * P:o_pen + 10 * P].view(torch.float32),
                               n_greedy)
+                if E:
+                    o_ids = o_edt + 5 * E
+                    skw["pen"] += ((d[o_ids:o_ids + N], d[o_ids + N:o_ids + 2 * N].view(torch.float32),
+                                    d[o_edt + E:o_ids].view(E, 4)) if N else None,
+                                   d[o_edt:o_edt + E].view(torch.float32))
+                    self.edited_steps += int(N > 0)
                 self.penalised_steps += int(P > 0)
             ev0 = self._start_event()
             te = time.perf_counter_ns()

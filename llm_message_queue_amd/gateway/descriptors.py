@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..ops.sampling import LP_TOP
+from ..ops.sampling import LE_MAX as EXT_LIST_MAX, LP_TOP   # (entries an extension list; alternatives a row)
 
 # --------------------------------------------------------------------------- descriptors
 K_DISPATCH, K_DONE, K_FAIL = 1, 2, 3     # K_FAIL: an evacuating backend hands a request back
@@ -31,7 +31,8 @@ K_HIST = 8
 DESC_HDR = 20       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/hi, gen, plen, flags, conv lo/hi,
 #                    dialog history length, decision - enq (us), processing timeout (ms),
 #                    sampling temperature (float32 bits), sampling seed lo/hi];
-#                    tier = tier | presence, frequency, repetition penalties << 4 (``pack_penalties``);
+#                    tier = tier | presence, frequency, repetition penalties << 4 (``pack_penalties``)
+#                           | EXTENSION; gen = gen | min_p permille << 16 (``pack_gen``);
 #                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN | top_k << 10 | top_p permille << 20
 #                            | LOGPROBS
 KV_MIGRATE = 1 << 8     # descriptor flag: hold the turn until its KV arrives from the home GPU
@@ -90,6 +91,62 @@ def unpack_penalties(col: int) -> tuple:
         return c, 0.0, 0.0, 1.0
     return (c & TIER_MASK, signed((c >> PRES_SHIFT) & 0x1FF, 9) / 100.0, signed((c >> FREQ_SHIFT) & 0x1FF, 9) / 100.0,
             (signed((c >> REP_SHIFT) & 0xFF, 8) + 100) / 100.0)
+# bit 30 of the tier column: the request has an extension stream -- its
+# ``allowed_token_ids`` and ``logit_bias`` lists -- that follows one tick later
+# as the third section (prefix, history, extension) of its K_HIST stream; the
+# serving GPU holds the request until it has arrived.  Every K_HIST row carries
+# the extension's length in col 16 (0: none).  ``unpack_penalties`` reads bits
+# 0-29 and is blind to it.
+EXTENSION = 1 << 30
+GEN_MASK = 0xFFFF       # col 9: tokens to generate (<= 4,096: the engine's largest ``max_ctx``) | min_p permille << 16
+MIN_P_SHIFT = 16
+
+
+def pack_gen(gen: int, min_p: float = 0.0) -> int:
+    """Col 9 of a K_DISPATCH row: ``gen`` and ``min_p`` as permille above it
+    (0: off; a value outside [0, 1] is off)."""
+    pm = int(round(float(min_p) * 1000.0)) if np.isfinite(min_p) else 0
+    return (min(max(int(gen), 0), GEN_MASK)) | ((pm if 0 <= pm <= 1000 else 0) << MIN_P_SHIFT)
+
+
+def unpack_gen(col: int) -> tuple:
+    """``(gen, min_p)`` of a col 9 value."""
+    c = int(col)
+    if c < 0:
+        return c, 0.0
+    pm = c >> MIN_P_SHIFT
+    return c & GEN_MASK, (pm / 1000.0 if pm <= 1000 else 0.0)
+
+
+
+
+def pack_extension(allowed, bias_ids, bias_vals) -> np.ndarray:
+    """The extension stream of a request, int32 words ``[n_allow, allow
+    ids..., n_bias, bias ids..., bias float32 bits...]``; no words at all for
+    a request with neither list.  A list is cut at ``EXT_LIST_MAX`` entries."""
+    al = np.asarray(allowed if allowed is not None else (), dtype=np.int32).reshape(-1)[:EXT_LIST_MAX]
+    bi = np.asarray(bias_ids if bias_ids is not None else (), dtype=np.int32).reshape(-1)[:EXT_LIST_MAX]
+    bv = np.asarray(bias_vals if bias_vals is not None else (), dtype=np.float32).reshape(-1)[:len(bi)]
+    bi = bi[:len(bv)]
+    if not len(al) and not len(bi):
+        return np.zeros(0, dtype=np.int32)
+    return np.concatenate([[len(al)], al, [len(bi)], bi, bv.view(np.int32)]).astype(np.int32)
+
+
+def unpack_extension(words) -> tuple:
+    """``(allowed int32, bias ids int32, bias values float32)`` of an
+    extension stream; counts that leave the stream are clamped to it."""
+    w = np.asarray(words, dtype=np.int32).reshape(-1)
+    none = np.zeros(0, dtype=np.int32)
+    if not len(w):
+        return none, none, np.zeros(0, dtype=np.float32)
+    na = min(max(int(w[0]), 0), EXT_LIST_MAX, len(w) - 1)
+    al = w[1:1 + na].copy()
+    rest = w[1 + na:]
+    nb = min(max(int(rest[0]), 0), EXT_LIST_MAX, (len(rest) - 1) // 2) if len(rest) else 0
+    return al, rest[1:1 + nb].copy(), rest[1 + nb:1 + 2 * nb].copy().view(np.float32)
+
+
 # serving GPU -> origin, ahead of the request's K_DONE (same FIFO): the
 # log-probabilities of a request dispatched with LOGPROBS, LP_WORDS int32 a
 # generated token -- id, lp (float32 bits), 5 alternative ids, their 5 lps --

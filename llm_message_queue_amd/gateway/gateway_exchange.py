@@ -27,12 +27,14 @@ from ..backend.engine import Request
 from ..models.message import Message, MessageStatus
 from ..parallel import planner
 from ..ops.sampling import LP_TOP
-from .descriptors import (DESC_HDR, DIALOG_TURN, FAIL_UNTOUCHED, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE, K_FAIL,
+from .descriptors import (DESC_HDR, DIALOG_TURN, EXTENSION, FAIL_UNTOUCHED, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE, K_FAIL,
                           K_HIST, K_LOGP, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, LOGPROBS, _get64, _put64, conv_key,
                           fill_logprob_row, logprob_chunks, pack_logprob_stream, pack_penalties, pack_truncation,
                           take_logprob_rows, unpack_penalties,
+                          pack_extension, pack_gen, unpack_extension, unpack_gen,
                           unpack_logprob_stream, unpack_truncation)
 
+_NO_EXT = np.zeros(0, dtype=np.int32)
 HIST_LEN_BITS = 20      # descriptor col 14: dialog history length | (compressed-context length << 20)
 from .latency import P_PLAN_LOCAL, P_PLAN_REMOTE
 from .request_table import HELD
@@ -163,9 +165,9 @@ class ExchangeMixin:
             buf = np.zeros((grant + done_for[j], width), dtype=np.int32)
             if rows:
                 ctx = self._fill_descs(buf[:len(rows)], rows, me, cap, migrate)
-                for m, (hist, pre) in zip(rows, ctx):
-                    if (hist is not None and len(hist)) or (pre is not None and len(pre)):
-                        self._hist_out.setdefault(j, []).append((m.handle, pre, hist))
+                for m, (hist, pre, ext) in zip(rows, ctx):
+                    if (hist is not None and len(hist)) or (pre is not None and len(pre)) or len(ext):
+                        self._hist_out.setdefault(j, []).append((m.handle, pre, hist, ext))
                 tname = f"gpu{j}"
                 for m in rows:
                     self.table.to_remote(m)
@@ -254,15 +256,18 @@ class ExchangeMixin:
                 fresh.extend(self._take_histories(src, hrows))
             disp = g[kinds == K_DISPATCH]
             if len(disp):
-                for r, fl in zip(self._foreign_requests(disp, cap), disp[:, 11].tolist()):
+                for r, fl, tc in zip(self._foreign_requests(disp, cap), disp[:, 11].tolist(), disp[:, 4].tolist()):
                     needs = (r.history is not None and len(r.history)) or (r.prefix is not None and len(r.prefix))
+                    ext = tc > 0 and bool(tc & EXTENSION)     # (its lists follow in its K_HIST stream)
                     if fl & KV_MIGRATE:
                         newly_held.append((r, (fl & 0xFF) - 1))
-                        if needs:                     # (the replay if the KV never lands)
+                        if needs or ext:              # (the replay if the KV never lands; the lists)
                             self._hist_wait[(r.meta[0], r.meta[1])] = r
-                    elif needs and not self._resident_ok(r):
+                    elif ext or (needs and not self._resident_ok(r)):
                         # not resident here: it replays its dialog, whose real
                         # tokens arrive from its router with the next exchange
+                        # (a request with an extension waits for it, dialog
+                        # turn or not, resident or not)
                         self._await_hist[(r.meta[0], r.meta[1])] = r
                         self._hist_wait[(r.meta[0], r.meta[1])] = r
                     else:
@@ -351,14 +356,16 @@ class ExchangeMixin:
                     migrate: Dict[int, int]) -> list:
         """K_DISPATCH descriptors of ``msgs`` into ``buf`` [n][width], the
         scalar fields as whole columns (one numpy op per field).  Returns
-        each message's dialog context (history, compressed-context prefix),
-        which follows as K_HIST rows with the next exchange."""
+        each message's dialog context and extension stream (history,
+        compressed-context prefix, ``pack_extension`` words), which follow as
+        K_HIST rows with the next exchange."""
         n = len(msgs)
         v = np.empty((n, 4), dtype=np.int64)      # handle, arrival, enq, conversation key
         small = np.zeros((n, 6), dtype=np.int64)  # tier, plen, flags, hist len, decision - enq (us)
         kv = self.kv_residency
         temp = np.zeros(n, dtype=np.float32)      # sampling temperature (float32 bits in col 17), seed
         seed = np.zeros(n, dtype=np.int64)
+        gens = np.zeros(n, dtype=np.int64)        # tokens to generate | min_p permille << 16 (col 9)
         prompts = []
         ctx = []
         for k, m in enumerate(msgs):
@@ -370,7 +377,6 @@ class ExchangeMixin:
             prompts.append(p)
             mf = migrate.get(id(m), -1)
             hist, pre = self._dialog_context(m) if cid else (None, None)
-            ctx.append((hist, pre))
             small[k, 0] = m.tier
             small[k, 1] = len(p)
             small[k, 2] = ((mf + 1) | KV_MIGRATE if mf >= 0 else 0) | (DIALOG_TURN if cid else 0)
@@ -381,17 +387,20 @@ class ExchangeMixin:
             small[k, 4] = min(0x7FFFFFFF, max(0, (m.popped_ns - m.enqueued_at) // 1000)) \
                 if (m.popped_ns and m.enqueued_at) else 0
             small[k, 5] = min(0x7FFFFFFF, self._timeout_ns(m) // 1_000_000)
-            temp[k], seed[k], top_k, top_p, logprobs, pens = self._sampling(m)
+            temp[k], seed[k], top_k, top_p, logprobs, pens, (min_p, bias, allowed) = self._sampling(m)
             small[k, 2] |= pack_truncation(top_k, top_p) | (LOGPROBS if logprobs >= 0 else 0)
+            ext = pack_extension(allowed, *bias) if (m.tier >= 0 and (len(allowed) or len(bias[0]))) else _NO_EXT
             if m.tier >= 0:
-                small[k, 0] |= pack_penalties(*pens)
+                small[k, 0] |= pack_penalties(*pens) | (EXTENSION if len(ext) else 0)
+            gens[k] = pack_gen(self.gen_tokens, min_p) if min_p else self.gen_tokens
+            ctx.append((hist, pre, ext))
         buf[:, 0] = K_DISPATCH
         _put64(buf, 1, v[:, 0])
         buf[:, 3] = origin
         buf[:, 4] = small[:, 0]
         _put64(buf, 5, v[:, 1])
         _put64(buf, 7, v[:, 2])
-        buf[:, 9] = self.gen_tokens
+        buf[:, 9] = gens
         buf[:, 10] = small[:, 1]
         buf[:, 11] = small[:, 2]
         _put64(buf, 12, v[:, 3])
@@ -409,22 +418,23 @@ class ExchangeMixin:
     def _hist_rows(self, j: int) -> int:
         """K_HIST rows this router owes GPU ``j`` this tick."""
         cap = self.prompt_cap
-        return sum(-(-((0 if pre is None else len(pre)) + (0 if h is None else len(h))) // cap)
-                   for _hd, pre, h in self._hist_pub.get(j, ()))
+        return sum(-(-((0 if pre is None else len(pre)) + (0 if h is None else len(h)) + len(ext)) // cap)
+                   for _hd, pre, h, ext in self._hist_pub.get(j, ()))
 
     def _hist_block(self, j: int, me: int, cap: int, width: int):
         """The K_HIST rows of the histories owed to ``j`` (None: none):
-        ``cap`` tokens a row, prefix then history."""
+        ``cap`` words a row, prefix then history then the extension stream
+        (``pack_extension``; its length in col 16 of every row)."""
         items = self._hist_pub.get(j)
         if not items:
             return None
         out = np.zeros((self._hist_rows(j), width), dtype=np.int32)
         k = 0
-        for h, pre, hist in items:
+        for h, pre, hist, ext in items:
             pre = np.zeros(0, np.int32) if pre is None else np.asarray(pre, dtype=np.int32)
             hist = np.zeros(0, np.int32) if hist is None else np.asarray(hist, dtype=np.int32)
-            allt = np.concatenate([pre, hist])
-            self.counters["hist_tokens_sent"] += len(allt)
+            allt = np.concatenate([pre, hist, ext]) if len(ext) else np.concatenate([pre, hist])
+            self.counters["hist_tokens_sent"] += len(pre) + len(hist)
             for off in range(0, len(allt), cap):
                 n = min(cap, len(allt) - off)
                 row = out[k]
@@ -434,35 +444,41 @@ class ExchangeMixin:
                 row[10] = n
                 row[14] = len(hist)
                 row[15] = len(pre)
+                row[16] = len(ext)
                 row[DESC_HDR:DESC_HDR + n] = allt[off:off + n]
                 k += 1
-        _put64(out, 1, [h for h, pre, hist in items
-                        for _ in range(-(-((0 if pre is None else len(pre)) + (0 if hist is None else len(hist)))
-                                         // cap))])
+        _put64(out, 1, [h for h, pre, hist, ext in items
+                        for _ in range(-(-((0 if pre is None else len(pre)) + (0 if hist is None else len(hist))
+                                           + len(ext)) // cap))])
         return out
 
     def _take_histories(self, src: int, rows: np.ndarray) -> List[Request]:
         """K_HIST rows from ``src``: fill the dialog history (and compressed
-        context) of its turns held here; returns the ones that only waited
-        for it (admitted this tick)."""
+        context), and the allow-list and logit bias of an extension stream, of
+        its requests held here; returns the ones that only waited for it
+        (admitted this tick)."""
         parts: Dict[int, np.ndarray] = {}
-        for h, off, n, hl, pl, row in zip(_get64(rows, 1).tolist(), rows[:, 4].tolist(), rows[:, 10].tolist(),
-                                          rows[:, 14].tolist(), rows[:, 15].tolist(), rows):
+        for h, off, n, hl, pl, el, row in zip(_get64(rows, 1).tolist(), rows[:, 4].tolist(), rows[:, 10].tolist(),
+                                              rows[:, 14].tolist(), rows[:, 15].tolist(), rows[:, 16].tolist(), rows):
             buf = parts.get(h)
             if buf is None:
-                buf = parts[h] = np.zeros(pl + hl, dtype=np.int32)
+                buf = parts[h] = np.zeros(pl + hl + el, dtype=np.int32)
             buf[off:off + n] = row[DESC_HDR:DESC_HDR + n]
             parts[h] = buf
             self._hist_len[(src, h)] = (hl, pl)
         ready = []
         for h, buf in parts.items():
             hl, pl = self._hist_len.pop((src, h))
-            self.counters["hist_tokens_recv"] += len(buf)
+            self.counters["hist_tokens_recv"] += pl + hl
             r = self._hist_wait.pop((src, h), None)
             if r is None:
                 continue                              # (admitted resident, cancelled or handed back)
             r.prefix = buf[:pl] if pl else None
-            r.history = buf[pl:] if hl else None
+            r.history = buf[pl:pl + hl] if hl else None
+            if len(buf) > pl + hl:
+                al, bi, bv = unpack_extension(buf[pl + hl:])
+                r.allowed = al if len(al) else None
+                r.logit_bias = (bi, bv) if len(bi) else None
             if self._await_hist.pop((src, h), None) is not None:
                 ready.append(r)
         return ready
@@ -494,6 +510,7 @@ class ExchangeMixin:
             hl, pl = hv & mask, hv >> HIST_LEN_BITS
             top_k, top_p = unpack_truncation(fl)
             tier, pres, freq, rep = unpack_penalties(tier)
+            gen, min_p = unpack_gen(gen)
             # the dialog context's LENGTH travels here (a resident turn only
             # needs it to check its KV is current); a turn that must replay
             # waits for the real tokens (K_HIST, next exchange), which replace
@@ -505,7 +522,7 @@ class ExchangeMixin:
                                timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN),
                                temperature=temps[k], seed=seeds[k], top_k=top_k, top_p=top_p,
                                logprobs=LP_TOP if fl & LOGPROBS else -1, presence_penalty=pres,
-                               frequency_penalty=freq, repetition_penalty=rep))
+                               frequency_penalty=freq, repetition_penalty=rep, min_p=min_p))
         return out
 
     def _owe_logprobs(self, origin: int, handle: int, r: Request) -> None:

@@ -32,8 +32,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..backend.engine import BackendEngine, Request
-from ..models.message import (PENALTY_KEYS, Message, MessageStatus, SamplingParseError, generation_record,
-                              logprobs_from_metadata, penalty_from_metadata,
+from ..models.message import (PENALTY_KEYS, Message, MessageStatus, SamplingParseError, allowed_from_metadata,
+                              generation_record, logit_bias_from_metadata, logprobs_from_metadata,
+                              min_p_from_metadata, penalty_from_metadata,
                               priority_name, sampling_from_metadata, truncation_from_metadata)
 from ..parallel import planner
 from ..parallel.comm import Comm, SoloComm
@@ -43,7 +44,7 @@ from ..utils.logging import get_logger
 
 NS = 1_000_000_000
 
-from .descriptors import (DESC_HDR, FAIL_UNTOUCHED, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE,  # noqa: F401
+from .descriptors import (DESC_HDR, FAIL_UNTOUCHED, GEN_MASK, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE,  # noqa: F401
                           K_FAIL, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, _get64, _put64, conv_key)
 from .latency import (PATHS, P_LANE, P_OWN, P_PLAN_LOCAL, P_PLAN_REMOTE, STAGES, LatencyRecorder,  # noqa: F401
                       StageRecorder, _hbin, hist_percentile)
@@ -92,6 +93,8 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         self.state_manager = state_manager
         self.prompt_cap = int(prompt_cap if prompt_cap is not None else cfg.backend.prompt_tokens)
         self.gen_tokens = int(gen_tokens if gen_tokens is not None else cfg.backend.gen_tokens)
+        if not 0 <= self.gen_tokens <= GEN_MASK:      # (col 9 of a dispatch row carries min_p above it)
+            raise ValueError(f"gen_tokens {self.gen_tokens} exceeds the dispatch row's {GEN_MASK}")
         q = cfg.queue
         self.qm = queue_manager or QueueManager(QueueManagerConfig(
             default_max_size=q.default_max_size, monitor_interval=q.monitor_interval,
@@ -175,8 +178,9 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         self._lp_parts: Dict[Tuple[int, int], np.ndarray] = {}
         # dialog histories owed to the GPUs this router dispatched turns to
         # (sent one tick later as K_HIST rows, counted in that tick's load vector)
-        self._hist_out: Dict[int, List[Tuple[int, np.ndarray, np.ndarray]]] = {}
-        self._hist_pub: Dict[int, List[Tuple[int, np.ndarray, np.ndarray]]] = {}
+        # entries: (handle, prefix, history, extension words)
+        self._hist_out: Dict[int, List[Tuple[int, np.ndarray, np.ndarray, np.ndarray]]] = {}
+        self._hist_pub: Dict[int, List[Tuple[int, np.ndarray, np.ndarray, np.ndarray]]] = {}
         # foreign turns that must replay their dialog, waiting for its history: (origin, handle) -> Request
         self._await_hist: Dict[Tuple[int, int], Request] = {}
         # every foreign turn a K_HIST is still expected for (also KV-held ones) and the lengths seen
@@ -453,32 +457,40 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             if len(prompt) else np.zeros(1, dtype=np.int32)
         ck = conv_key(m.conversation_id) if self.kv_residency else -1
         hist, pre = self._dialog_context(m)
-        temp, seed, top_k, top_p, logprobs, pens = self._sampling(m)
+        temp, seed, top_k, top_p, logprobs, pens, (min_p, bias, allowed) = self._sampling(m)
         return Request(req_id=m.handle, prompt=p, gen_tokens=self.gen_tokens, tier=tier, meta=m, conv=ck,
                        history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed,
                        top_k=top_k, top_p=top_p, logprobs=logprobs, presence_penalty=pens[0],
-                       frequency_penalty=pens[1], repetition_penalty=pens[2])
+                       frequency_penalty=pens[1], repetition_penalty=pens[2], min_p=min_p,
+                       logit_bias=bias if len(bias[0]) else None, allowed=allowed if len(allowed) else None)
+
+    _NO_ELIGIBILITY = (0.0, (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32)), np.zeros(0, dtype=np.int32))
 
     @staticmethod
-    def _sampling(m: Message) -> Tuple[float, int, int, float, int, Tuple[float, float, float]]:
+    def _sampling(m: Message) -> Tuple[float, int, int, float, int, Tuple[float, float, float], tuple]:
         """The message's effective ``(temperature, seed, top_k, top_p,
-        logprobs, (presence, frequency, repetition penalty))``
+        logprobs, (presence, frequency, repetition penalty), (min_p,
+        (logit_bias ids, values), allowed_token_ids))``
         (``metadata.sampling``), lenient: this path also serves
         messages no route validated (the native ingress), so a bad
         temperature or seed falls back to greedy, a bad ``top_k`` / ``top_p``
         turns the truncation off, a bad ``logprobs`` turns the
-        log-probabilities off (-1), a bad penalty turns that penalty off,
-        and each is reported in
+        log-probabilities off (-1), a bad penalty turns that penalty off, a
+        bad ``min_p`` / ``logit_bias`` / ``allowed_token_ids`` turns that key
+        off, and each is reported in
         ``metadata["sampling_error"]``.  A message that asked for sampling
         gets the effective values written back, so a client can replay it:
         ``top_k`` / ``top_p`` only where they are active (with a temperature,
-        and not off), a penalty only where it is not off (greedy or not),
+        and not off; ``min_p`` likewise), a penalty only where it is not
+        off (greedy or not), ``logit_bias`` (its non-zero entries) and
+        ``allowed_token_ids`` only where they are in effect (greedy or not),
         and ``logprobs`` only where the message named it, so a
         message that named none of them keeps exactly ``{"temperature",
         "seed"}``."""
         md = m.metadata
         if not md or "sampling" not in md:
-            return 0.0, 0, 0, 1.0, -1, (0.0, 0.0, 1.0)    # greedy (the default traffic): the seed is never read
+            # greedy (the default traffic): the seed is never read
+            return 0.0, 0, 0, 1.0, -1, (0.0, 0.0, 1.0), Gateway._NO_ELIGIBILITY
         try:
             temp, seed = sampling_from_metadata(md, m.id)
         except SamplingParseError as e:
@@ -501,8 +513,17 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             except SamplingParseError as e:
                 md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
                 pens.append(off)
+        elig = []
+        for parse, off in zip((min_p_from_metadata, logit_bias_from_metadata, allowed_from_metadata),
+                              Gateway._NO_ELIGIBILITY):
+            try:
+                elig.append(parse(md))
+            except SamplingParseError as e:
+                md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
+                elig.append(off)
+        min_p, bias, allowed = elig
         if temp <= 0:
-            top_k, top_p = 0, 1.0                 # (accepted, without effect)
+            top_k, top_p, min_p = 0, 1.0, 0.0     # (accepted, without effect)
         eff = {"temperature": temp, "seed": seed}
         if top_k > 0:
             eff["top_k"] = top_k
@@ -513,8 +534,14 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         for (key, (_lo, _hi, off)), v in zip(PENALTY_KEYS.items(), pens):
             if v != off:
                 eff[key] = v
+        if min_p > 0:
+            eff["min_p"] = min_p
+        if len(bias[0]):
+            eff["logit_bias"] = {str(int(t)): float(v) for t, v in zip(*bias)}
+        if len(allowed):
+            eff["allowed_token_ids"] = [int(t) for t in allowed]
         md["sampling"] = eff
-        return temp, seed, top_k, top_p, logprobs, tuple(pens)
+        return temp, seed, top_k, top_p, logprobs, tuple(pens), (min_p, bias, allowed)
 
     @staticmethod
     def _attach_generation(m: Message, tokens, lp, top_ids, top_lp) -> None:

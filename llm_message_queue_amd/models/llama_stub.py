@@ -259,7 +259,9 @@ class LlamaStub:
         = (rows int64 [R] into the sampled rows, top_k int32 [R], top_p
         float32 [R]): those rows ask for top-k / top-p and are drawn again,
         from their own logits, by ``ops.truncated_head`` (the head over all
-        sampled rows runs as without it; their first draw is overwritten).
+        sampled rows runs as without it; their first draw is overwritten).  A
+        fourth element, log_min_p float32 [R] (``ops.sampling.min_p_log``; -inf:
+        off), adds ``min_p``.
         ``logp`` (int64 [L] rows into the sampled rows, sampling or greedy):
         those rows ask for log-probabilities; the result is then ``(tokens,
         lp float32 [L][6], ids int32 [L][5])`` with ``ops.logprob_head``'s
@@ -274,7 +276,13 @@ class LlamaStub:
         penalty, greedy or sampling, the first ``n_greedy`` of them greedy.
         Those rows are drawn again by ``ops.penalised_head`` with their own
         ``top_k`` / ``top_p`` and overwrite their first draw; the caller keeps
-        them out of ``trunc``, so a row is drawn again once.
+        them out of ``trunc``, so a row is drawn again once.  Two more
+        elements, ``edit`` = (ids int32 [N], vals float32 [N], spans int32
+        [P][4]) or None and log_min_p float32 [P] or None, carry the rows'
+        allow lists and logit biases (``ops.gemm.logit_edit``) and their
+        ``min_p``; rows with only those have a penalty span whose slot is -1,
+        and ``hist`` is None where no slot has a penalty (nothing is recorded
+        or read then).
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -285,7 +293,7 @@ class LlamaStub:
         where the tiles cannot fill the partition.  ``quant`` (a model built
         with ``small_weights="fp8"``): every layer GEMM of this forward reads
         the FP8 weights (``hidden``); the head stays bf16."""
-        if pen is not None and pen[1].numel():
+        if pen is not None and pen[0] is not None and pen[1].numel():
             self.ops.history_record(pen[0], tokens, pos, slot, pen[1])
         if self.prune_last and self.residual_in_gemm:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus,
@@ -298,14 +306,18 @@ class LlamaStub:
             out = self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
                                        min_rows=1 if hand else 256)
             if trunc is not None:
-                rows, top_k, top_p = trunc
+                rows, top_k, top_p = trunc[:3]
+                kw = {"log_min_p": trunc[3]} if len(trunc) > 3 and trunc[3] is not None else {}
                 out.index_copy_(0, rows, self.ops.truncated_head(
                     sel.index_select(0, rows), self.lm_head, inv_temp.index_select(0, rows),
-                    keys.index_select(0, rows), top_k, top_p))
+                    keys.index_select(0, rows), top_k, top_p, **kw))
         else:
             out = self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
         if pen is not None and pen[2].numel():
-            hist, _, rows, spans, params, top_k, top_p, n_greedy = pen
+            hist, _, rows, spans, params, top_k, top_p, n_greedy = pen[:8]
+            kw = {}
+            if len(pen) > 8 and (pen[8] is not None or pen[9] is not None):
+                kw = {"edit": pen[8], "log_min_p": pen[9]}
             P = rows.numel()
             if inv_temp is not None and keys is not None:
                 it, kk = inv_temp.index_select(0, rows), keys.index_select(0, rows)
@@ -314,7 +326,7 @@ class LlamaStub:
                 kk = torch.zeros((P, 2), dtype=torch.int32, device=out.device)
             out.index_copy_(0, rows, self.ops.penalised_head(
                 sel.index_select(0, rows), self.lm_head, it, kk, top_k, top_p, hist, spans, params,
-                n_greedy=n_greedy))
+                n_greedy=n_greedy, **kw))
         if logp is None:
             return out
         lp, ids = self.ops.logprob_head(sel.index_select(0, logp), self.lm_head, out.index_select(0, logp))

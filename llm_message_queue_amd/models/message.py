@@ -435,6 +435,99 @@ def penalties_from_metadata(md: Any) -> tuple:
     return tuple(penalty_from_metadata(md, k) for k in PENALTY_KEYS)
 
 
+from ..ops.sampling import LE_MAX as EDIT_LIST_MAX  # noqa: E402  (entries the edit kernel takes a list)
+LOGIT_BIAS_MAX = 100.0
+TOKEN_ID_END = 1 << 31
+
+
+def _sampling_object(md: Any):
+    sp = md.get("sampling") if isinstance(md, dict) else None
+    if sp is not None and not isinstance(sp, dict):
+        raise SamplingParseError("sampling must be an object")
+    return sp
+
+
+def min_p_from_metadata(md: Any) -> float:
+    """``min_p`` of a message's ``metadata.sampling`` object: a number in [0,
+    1], rounded to thousandths; 0 (the default, and any value that rounds to
+    it) is off.  It takes effect only with a ``temperature`` > 0: a token
+    stays eligible iff its probability is at least ``min_p`` times the most
+    likely token's.  Raises ``SamplingParseError`` on anything else."""
+    sp = _sampling_object(md)
+    if sp is None or "min_p" not in sp:
+        return 0.0
+    v = sp["min_p"]
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not (0.0 <= v <= 1.0):
+        raise SamplingParseError("sampling.min_p must be a number in [0, 1]")
+    return int(round(float(v) * 1000.0)) / 1000.0
+
+
+def _token_id(x: Any, what: str) -> int:
+    if isinstance(x, bool) or not isinstance(x, int) or not (0 <= x < TOKEN_ID_END):
+        raise SamplingParseError(f"sampling.{what} must be integers in [0, 2^31)")
+    return int(x)
+
+
+def logit_bias_from_metadata(md: Any) -> tuple:
+    """``logit_bias`` of a message's ``metadata.sampling`` object: ``(ids
+    int32 [n], values float32 [n])``, n <= 64, in the object's order and
+    without the entries whose value is 0; two empty arrays where the key is
+    absent.  The object maps a token id -- a JSON key, so the integer's
+    canonical decimal string: no sign, no leading zero -- in [0, 2^31) to a
+    number in [-100, 100] that is added to the token's logit as
+    ``float32(value)``, with or without a ``temperature``.  Raises
+    ``SamplingParseError`` on anything else."""
+    import numpy as np
+    sp = _sampling_object(md)
+    ids, vals = [], []
+    if sp is not None and "logit_bias" in sp:
+        lb = sp["logit_bias"]
+        if not isinstance(lb, dict) or len(lb) > EDIT_LIST_MAX:
+            raise SamplingParseError(f"sampling.logit_bias must be an object of at most {EDIT_LIST_MAX} entries")
+        for k, v in lb.items():
+            # (at most the 10 digits of 2^31 - 1 before any conversion: int() itself refuses very long strings
+            #  with a plain ValueError)
+            if not isinstance(k, str) or not 0 < len(k) <= 10 or not k.isascii() or not k.isdigit() \
+                    or k != str(int(k)):
+                raise SamplingParseError("sampling.logit_bias keys must be token ids in canonical decimal form")
+            t = _token_id(int(k), "logit_bias keys")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) \
+                    or not (-LOGIT_BIAS_MAX <= v <= LOGIT_BIAS_MAX):
+                raise SamplingParseError(f"sampling.logit_bias values must be numbers in [-{LOGIT_BIAS_MAX:g}, "
+                                         f"{LOGIT_BIAS_MAX:g}]")
+            if np.float32(v) != 0:
+                ids.append(t)
+                vals.append(v)
+    return np.asarray(ids, dtype=np.int32), np.asarray(vals, dtype=np.float32)
+
+
+def allowed_from_metadata(md: Any):
+    """``allowed_token_ids`` of a message's ``metadata.sampling`` object: an
+    int32 array of 1..64 distinct token ids in [0, 2^31), the only tokens
+    that can be picked or drawn, greedy or sampling; an empty array where
+    the key is absent.  Raises ``SamplingParseError`` on anything else."""
+    import numpy as np
+    sp = _sampling_object(md)
+    if sp is None or "allowed_token_ids" not in sp:
+        return np.zeros(0, dtype=np.int32)
+    al = sp["allowed_token_ids"]
+    if not isinstance(al, (list, tuple)) or not (1 <= len(al) <= EDIT_LIST_MAX):
+        raise SamplingParseError(f"sampling.allowed_token_ids must be a list of 1 to {EDIT_LIST_MAX} token ids")
+    ids = [_token_id(x, "allowed_token_ids") for x in al]
+    if len(set(ids)) != len(ids):
+        raise SamplingParseError("sampling.allowed_token_ids must be distinct")
+    return np.asarray(ids, dtype=np.int32)
+
+
+def eligibility_from_metadata(md: Any) -> tuple:
+    """``(min_p, logit_bias, allowed_token_ids)`` of a message's
+    ``metadata.sampling`` object (:func:`min_p_from_metadata`,
+    :func:`logit_bias_from_metadata`, :func:`allowed_from_metadata`).  Order
+    of the whole object: penalties, ``allowed_token_ids``, ``logit_bias``,
+    temperature, ``top_k``, ``top_p``, ``min_p``, then the draw."""
+    return min_p_from_metadata(md), logit_bias_from_metadata(md), allowed_from_metadata(md)
+
+
 def generation_record(tokens, token_logprobs, top_ids, top_logprobs, n: int) -> Dict[str, Any]:
     """``metadata.generation`` of a completed message that asked for
     ``logprobs = n``: the generated tokens, their log-probabilities and, for

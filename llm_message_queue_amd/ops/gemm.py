@@ -666,8 +666,9 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, inv_temp: torch.Tensor, key
 
 
 def sample_truncated(logits: torch.Tensor, inv_temp: torch.Tensor, keys: torch.Tensor, top_k: torch.Tensor,
-                     top_p: torch.Tensor, vocab: int = None, out: torch.Tensor = None) -> torch.Tensor:
-    """Top-k / top-p sampling over given bf16 ``logits`` [R][ld] -> int32 [R]
+                     top_p: torch.Tensor, vocab: int = None, out: torch.Tensor = None,
+                     log_min_p: torch.Tensor = None) -> torch.Tensor:
+    """Top-k / top-p / min-p sampling over given bf16 ``logits`` [R][ld] -> int32 [R]
     (``csrc/kernels/sample_truncate_kernels.h`` holds the contract,
     ``ops.sampling.sample_truncated_reference`` is its twin): per row, top-k
     then top-p select whole groups of equal values, and the pick is the argmax
@@ -675,7 +676,8 @@ def sample_truncated(logits: torch.Tensor, inv_temp: torch.Tensor, keys: torch.T
     the columns that count (default ld; the rest of a row is padding), ``ld %
     8 == 0``.  ``inv_temp`` float32 [>= R] (> 0), ``keys`` 32-bit [>= R][2] =
     ``ops.sampling.row_keys``, ``top_k`` int32 [>= R] (0: off), ``top_p``
-    float32 [>= R] (>= 1: off)."""
+    float32 [>= R] (>= 1: off), ``log_min_p`` float32 [>= R] or None:
+    ``ops.sampling.min_p_log`` of the row's ``min_p`` (-inf, or None: off)."""
     _check(logits, "logits")
     if logits.dim() != 2:
         raise ValueError("sample_truncated: logits must be [R][ld]")
@@ -684,7 +686,9 @@ def sample_truncated(logits: torch.Tensor, inv_temp: torch.Tensor, keys: torch.T
     if not 0 < V <= ld or ld % 8:
         raise ValueError(f"sample_truncated: needs 0 < vocab <= ld and ld % 8 == 0 (vocab={V} ld={ld})")
     for t, n, dt in ((inv_temp, "inv_temp", (torch.float32,)), (top_k, "top_k", (torch.int32,)),
-                     (top_p, "top_p", (torch.float32,))):
+                     (top_p, "top_p", (torch.float32,)), (log_min_p, "log_min_p", (torch.float32,))):
+        if t is None:
+            continue
         if t.dtype not in dt or t.dim() != 1 or t.numel() < R or not t.is_contiguous() or t.device != logits.device:
             raise ValueError(f"sample_truncated: {n} must be contiguous {dt[0]} [>= R] on the logits' device")
     if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 2 or keys.shape[1] != 2 \
@@ -695,7 +699,8 @@ def sample_truncated(logits: torch.Tensor, inv_temp: torch.Tensor, keys: torch.T
         raise ValueError("sample_truncated: out must be contiguous int32 [>= R] on the logits' device")
     _native.require_hipops().sample_truncated(logits.data_ptr(), R, V, ld, inv_temp.data_ptr(), keys.data_ptr(),
                                               top_k.data_ptr(), top_p.data_ptr(), y.data_ptr(),
-                                              torch.cuda.current_stream(logits.device).cuda_stream)
+                                              torch.cuda.current_stream(logits.device).cuda_stream,
+                                              log_min_p.data_ptr() if log_min_p is not None else 0)
     return y[:R]
 
 
@@ -826,6 +831,38 @@ def history_record(hist: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, slo
         _native.require_hipops().history_record(hist.data_ptr(), hist.shape[0], hist.shape[1], tok.data_ptr(),
                                                 pos.data_ptr(), slot.data_ptr(), T, rows.data_ptr(), Q,
                                                 torch.cuda.current_stream(hist.device).cuda_stream)
+
+
+from .sampling import LE_MAX  # noqa: E402  (entries a list)
+
+
+def logit_edit(logits: torch.Tensor, ids: torch.Tensor, vals: torch.Tensor, spans: torch.Tensor,
+               vocab: int = None) -> torch.Tensor:
+    """Edit bf16 ``logits`` [R][ld] in place by their rows' allow lists and
+    additive biases (``csrc/kernels/logit_edit_kernels.h`` holds the contract,
+    ``ops.sampling.logit_edit_reference`` is its bit-exact twin).  ``ids``
+    int32 [N] and ``vals`` float32 [N] are the flat lists, ``spans`` int32
+    [>= R][4] = (allow_off, n_allow, bias_off, n_bias): row r's allow list is
+    ``ids[allow_off:allow_off + n_allow]``, its bias entries ``(ids[bias_off +
+    i], vals[bias_off + i])``; a count is capped at LE_MAX and a span clamped
+    to the lists.  ``vocab``: the columns that count (default ld).  Returns
+    ``logits``."""
+    R, ld, V = _pen_logits("logit_edit", logits, vocab)
+    if logits.data_ptr() % 16:
+        raise ValueError("logit_edit: logits must be 16-byte aligned")
+    for t, n, dt in ((ids, "ids", torch.int32), (vals, "vals", torch.float32)):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != logits.device:
+            raise ValueError(f"logit_edit: {n} must be contiguous {dt} [N] on the logits' device")
+    if ids.numel() != vals.numel():
+        raise ValueError("logit_edit: ids and vals must have one length")
+    if spans.dtype != torch.int32 or spans.dim() != 2 or spans.shape[1] != 4 or spans.shape[0] < R \
+            or not spans.is_contiguous() or spans.device != logits.device:
+        raise ValueError("logit_edit: spans must be contiguous int32 [>= R][4] on the logits' device")
+    if R and ids.numel():
+        _native.require_hipops().logit_edit(logits.data_ptr(), R, V, ld, ids.data_ptr(), vals.data_ptr(),
+                                            ids.numel(), spans.data_ptr(),
+                                            torch.cuda.current_stream(logits.device).cuda_stream)
+    return logits
 
 
 def sample_bits(keys: torch.Tensor, n0: int, count: int) -> torch.Tensor:

@@ -111,9 +111,10 @@ class HipOps:
         sc = torch.where(it != 0, lg.double() * it.double() - torch.log(e), lg.double())
         return torch.argmax(sc, dim=-1).to(torch.int32)
 
-    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p):
-        """Tokens of the LM head under top-k / top-p sampling (int32 [R];
-        ``ops.gemm.sample_truncated``) for the rows that ask for it.  Their
+    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p, log_min_p=None):
+        """Tokens of the LM head under top-k / top-p / min-p sampling (int32
+        [R]; ``ops.gemm.sample_truncated``; ``log_min_p`` float32 [R] or None:
+        ``ops.sampling.min_p_log``) for the rows that ask for it.  Their
         logits come from the 256x256 tile kernel's store epilogue whatever R
         is -- no split-K, no skinny kernel -- so a row's logits are the bf16
         rounding of the fp32 accumulators the fused head scores and do not
@@ -129,7 +130,8 @@ class HipOps:
             if V % 8:
                 lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
             lg = lg.contiguous()
-        return G.sample_truncated(lg, inv_temp.contiguous(), keys.contiguous(), top_k, top_p, vocab=V)
+        return G.sample_truncated(lg, inv_temp.contiguous(), keys.contiguous(), top_k, top_p, vocab=V,
+                                  log_min_p=None if log_min_p is None else log_min_p.contiguous())
 
     def logprob_head(self, x, w, tok):
         """Log-probabilities of the LM head for the rows that ask for them:
@@ -151,9 +153,11 @@ class HipOps:
             lg = lg.contiguous()
         return G.token_logprobs(lg, tok.to(torch.int32).contiguous(), vocab=V)
 
-    def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None):
-        """Tokens of the LM head (int32 [R]) for the rows that ask for a
-        presence / frequency / repetition penalty.  Their logits come as
+    def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None, edit=None,
+                       log_min_p=None):
+        """Tokens of the LM head (int32 [R]) for the edited rows: those that
+        ask for a presence / frequency / repetition penalty, an allow-list or
+        a logit bias.  Their logits come as
         ``truncated_head``'s do (the tile kernel's store epilogue whatever R
         is, ``F.linear`` for a shape it refuses), in a scratch entry of their
         own; ``ops.gemm.penalise`` edits them in place by each row's history
@@ -162,7 +166,13 @@ class HipOps:
         ``inv_temp > 0`` is drawn by ``ops.gemm.sample_truncated`` under its
         ``top_k`` / ``top_p`` (0 / 1.0: none) and a greedy row picked by
         ``ops.gemm.penalised_argmax``; the sampler never sees a greedy row
-        (its contract wants ``inv_temp > 0``).  ``n_greedy``: the rows come
+        (its contract wants ``inv_temp > 0``).  ``edit`` = (ids int32 [N],
+        vals float32 [N], spans int32 [R][4]): the rows' allow lists and
+        biases, applied by ``ops.gemm.logit_edit`` after the penalties
+        (``csrc/kernels/logit_edit_kernels.h``); ``log_min_p`` float32 [R]:
+        the sampling rows' min-p.  A row without a penalty has a span whose
+        slot is -1 and reads no history; ``hist`` None: no row has one.
+        ``n_greedy``: the rows come
         greedy first, so many of them (the engine lists them so).  Without
         it the rows are partitioned here, which reads ``inv_temp`` back on
         the host (a synchronisation)."""
@@ -176,6 +186,10 @@ class HipOps:
                 order = torch.argsort(hot.to(torch.uint8), stable=True)
                 x, inv_temp, keys, top_k, top_p, spans, params = (
                     t[:R].index_select(0, order) for t in (x, inv_temp, keys, top_k, top_p, spans, params))
+                if edit is not None:
+                    edit = (edit[0], edit[1], edit[2][:R].index_select(0, order))
+                if log_min_p is not None:
+                    log_min_p = log_min_p[:R].index_select(0, order)
         if G.supported(R, V, x.shape[1]):
             buf, = G._scratch(x.device, _stream(x), "pen", (R * V, 0, torch.empty, torch.bfloat16))
             lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
@@ -184,12 +198,16 @@ class HipOps:
             if V % 8:
                 lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
             lg = lg.contiguous()
-        G.penalise(lg, hist, spans.contiguous(), params.contiguous(), vocab=V)
+        if hist is not None:
+            G.penalise(lg, hist, spans.contiguous(), params.contiguous(), vocab=V)
+        if edit is not None:
+            G.logit_edit(lg, edit[0].contiguous(), edit[1].contiguous(), edit[2].contiguous(), vocab=V)
         g = min(max(int(n_greedy), 0), R)
         out = torch.zeros(R, dtype=torch.int32, device=x.device)
         if g < R:
             G.sample_truncated(lg[g:], inv_temp.contiguous()[g:], keys.contiguous()[g:], top_k.contiguous()[g:],
-                               top_p.contiguous()[g:], vocab=V, out=out[g:])
+                               top_p.contiguous()[g:], vocab=V, out=out[g:],
+                               log_min_p=None if log_min_p is None else log_min_p.contiguous()[g:])
         if g:
             G.penalised_argmax(lg[:g], vocab=V, out=out)
         return out if order is None else torch.empty_like(out).index_copy_(0, order, out)
@@ -352,7 +370,7 @@ class RefOps:
         # a greedy row is exactly this class's greedy_head (bf16 logits)
         return torch.where(it != 0, picks, self.greedy_head(x, w, fused, min_rows))
 
-    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p):
+    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p, log_min_p=None):
         """Reference of ``HipOps.truncated_head``: fp32 logits rounded to bf16,
         then the numpy twin (``ops.sampling.sample_truncated_reference``)."""
         from .sampling import sample_truncated_reference
@@ -360,7 +378,8 @@ class RefOps:
         lg = (x.float() @ w.float().t()).to(torch.bfloat16).float().cpu().numpy()
         kk = keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
         picks = sample_truncated_reference(lg, inv_temp[:R].cpu().numpy(), kk, top_k[:R].cpu().numpy(),
-                                           top_p[:R].cpu().numpy())
+                                           top_p[:R].cpu().numpy(),
+                                           log_min_p=None if log_min_p is None else log_min_p[:R].cpu().numpy())
         return torch.from_numpy(picks).to(x.device)
 
     def logprob_head(self, x, w, tok):
@@ -372,24 +391,33 @@ class RefOps:
         return (torch.from_numpy(lp.astype("float32")).to(x.device),
                 torch.from_numpy(ids.astype("int32")).to(x.device))
 
-    def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None):
+    def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None, edit=None,
+                       log_min_p=None):
         """Reference of ``HipOps.penalised_head``: fp32 logits rounded to bf16,
-        the numpy twin of the edit (``ops.sampling.penalise_rows_reference``),
+        the numpy twins of the edits (``ops.sampling.penalise_rows_reference``,
+        ``logit_edit_reference``),
         then ``sample_truncated_reference`` for a row with ``inv_temp > 0``
         and ``penalised_pick_reference`` for a greedy one."""
-        from .sampling import (bf16_values, penalise_rows_reference, penalised_pick_reference,
+        from .sampling import (bf16_values, logit_edit_reference, penalise_rows_reference, penalised_pick_reference,
                                sample_truncated_reference)
         R, V = x.shape[0], w.shape[0]
         lg = (x.float() @ w.float().t()).to(torch.bfloat16).cpu().contiguous()
-        bits = penalise_rows_reference(lg.view(torch.int16).numpy().view("uint16"), V, hist.cpu().numpy(),
-                                       spans[:R].cpu().numpy(), params[:R].cpu().numpy())
+        bits = lg.view(torch.int16).numpy().view("uint16")
+        if hist is not None:
+            bits = penalise_rows_reference(bits, V, hist.cpu().numpy(), spans[:R].cpu().numpy(),
+                                           params[:R].cpu().numpy())
+        if edit is not None:
+            bits = logit_edit_reference(bits, V, edit[0].cpu().numpy(), edit[1].cpu().numpy(),
+                                        edit[2][:R].cpu().numpy())
         it = inv_temp[:R].cpu().numpy()
         picks = penalised_pick_reference(bits, V)
         hot = it > 0
         if hot.any():
             kk = keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
             picks[hot] = sample_truncated_reference(bf16_values(bits)[hot], it[hot], kk[hot],
-                                                    top_k[:R].cpu().numpy()[hot], top_p[:R].cpu().numpy()[hot])
+                                                    top_k[:R].cpu().numpy()[hot], top_p[:R].cpu().numpy()[hot],
+                                                    log_min_p=None if log_min_p is None
+                                                    else log_min_p[:R].cpu().numpy()[hot])
         return torch.from_numpy(picks).to(x.device)
 
     def history_record(self, hist, tok, pos, slot, rows):

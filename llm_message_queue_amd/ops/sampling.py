@@ -20,6 +20,10 @@ Penalties: :func:`penalise_reference` is the bit-exact twin of the edit in
 ``csrc/kernels/penalty_kernels.h`` (over bf16 bit patterns, so padding and
 non-finite values compare too), :func:`penalised_pick_reference` that of its
 greedy pick.
+
+Allow-lists and biases: :func:`logit_edit_reference` is the bit-exact twin of
+``csrc/kernels/logit_edit_kernels.h``; ``min_p`` is one more keep rule of
+:func:`truncation_keep`, evaluated in float32 exactly as the device does.
 """
 from __future__ import annotations
 
@@ -98,8 +102,17 @@ def inv_temperature(temperature) -> np.ndarray:
     return np.where(t > 0, 1.0 / np.where(t > 0, t, 1.0), 0.0).astype(np.float32)
 
 
-def truncation_keep(logits_bf16, inv_temp, top_k, top_p) -> np.ndarray:
-    """bool [V]: the columns top-k then top-p keep of one row of bf16 logits
+def min_p_log(min_p) -> np.ndarray:
+    """float32 ``log(permille / 1000)`` of ``min_p`` rounded to thousandths:
+    what the truncated sampler takes as ``log_min_p``.  -inf (off) for a value
+    that rounds to 0 permille, 0.0 for 1.0."""
+    pm = np.rint(np.clip(np.nan_to_num(np.asarray(min_p, dtype=np.float64)), 0.0, 1.0) * 1000.0)
+    with np.errstate(divide="ignore"):
+        return np.log(pm / 1000.0).astype(np.float32)
+
+
+def truncation_keep(logits_bf16, inv_temp, top_k, top_p, min_p=None, log_min_p=None) -> np.ndarray:
+    """bool [V]: the columns top-k, top-p and then min-p keep of one row of bf16 logits
     (an array of bf16-representable values), in float64 -- the twin of the
     selection in ``csrc/kernels/sample_truncate_kernels.h``, which holds the
     contract.  The distinct finite values in descending order are groups with
@@ -107,7 +120,13 @@ def truncation_keep(logits_bf16, inv_temp, top_k, top_p) -> np.ndarray:
     the groups before it (0: off), top-p a group top-k kept iff the mass
     ``count * exp((value - max) * inv_temp)`` of the kept groups before it is
     below ``top_p`` times their total (>= 1: off); the first group always
-    stays.  A NaN or infinite logit is never kept."""
+    stays.  A NaN or infinite logit is never kept.  ``log_min_p`` (float32,
+    what the kernel takes; or ``min_p``, a ratio converted by
+    :func:`min_p_log`; None or -inf: off): a column of value ``v`` stays iff
+    ``fl(fl(v - max) * inv_temp) >= log_min_p``, both operations in float32 as
+    on the device, so this rule is exact."""
+    if log_min_p is None and min_p is not None:
+        log_min_p = min_p_log(min_p)
     v = np.asarray(logits_bf16, dtype=np.float64).reshape(-1)
     fin = np.isfinite(v)
     if not fin.any():
@@ -122,25 +141,33 @@ def truncation_keep(logits_bf16, inv_temp, top_k, top_p) -> np.ndarray:
         mass = np.where(keep, counts * np.exp((vals - vals[0]) * float(np.float32(inv_temp))), 0.0)
         keep &= np.cumsum(mass) - mass < tp * mass.sum()
     keep[0] = True
-    return fin & (v >= vals[keep].min())
+    kept = fin & (v >= vals[keep].min())
+    if log_min_p is not None and not np.float32(log_min_p) == np.float32(-np.inf):
+        with np.errstate(all="ignore"):
+            d = np.where(fin, v, vals[0]).astype(np.float32) - np.float32(vals[0])
+            kept &= d * np.float32(inv_temp) >= np.float32(log_min_p)
+    return kept
 
 
-def sample_truncated_reference(logits, inv_temp, keys, top_k, top_p) -> np.ndarray:
+def sample_truncated_reference(logits, inv_temp, keys, top_k, top_p, min_p=None, log_min_p=None) -> np.ndarray:
     """The reference of the truncated sampler: int32 [R] picks over bf16
     ``logits`` [R][V], per row the argmax of ``logit * inv_temp + G`` over the
     columns :func:`truncation_keep` keeps (float64 scores, ties to the lower
-    column; 0 for a row that keeps nothing).  ``top_k`` / ``top_p``: per row
-    or one value for all."""
+    column; 0 for a row that keeps nothing).  ``top_k`` / ``top_p`` /
+    ``log_min_p`` (or ``min_p``, a ratio): per row or one value for all."""
+    if log_min_p is None and min_p is not None:
+        log_min_p = min_p_log(min_p)
     lg = np.asarray(logits, dtype=np.float64)
     R, V = lg.shape
     it = np.broadcast_to(np.asarray(inv_temp, dtype=np.float32), (R,))
     tk = np.broadcast_to(np.asarray(top_k, dtype=np.int64), (R,))
     tp = np.broadcast_to(np.asarray(top_p, dtype=np.float32), (R,))
+    lm = None if log_min_p is None else np.broadcast_to(np.asarray(log_min_p, dtype=np.float32), (R,))
     keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
     cols = np.arange(V, dtype=np.uint32)
     out = np.zeros(R, dtype=np.int32)
     for r in range(R):
-        keep = truncation_keep(lg[r], it[r], tk[r], tp[r])
+        keep = truncation_keep(lg[r], it[r], tk[r], tp[r], log_min_p=None if lm is None else lm[r])
         if keep.any():
             sc = np.where(keep, lg[r], 0.0) * float(it[r]) + gumbel(keys[r:r + 1], cols)[0]
             out[r] = np.where(keep, sc, -np.inf).argmax()
@@ -324,3 +351,47 @@ def penalised_pick_reference(bits, vocab: int) -> np.ndarray:
     v = bf16_values(np.asarray(bits, dtype=np.uint16).reshape(len(bits), -1)[:, :int(vocab)]).astype(np.float64)
     v = np.where(np.isfinite(v), v, -np.inf)
     return np.where(np.isfinite(v.max(axis=1)), v.argmax(axis=1), 0).astype(np.int32)
+
+
+# entries a list: the package's one copy of csrc/kernels/logit_edit_kernels.h's LE_MAX (the parser's cap, the
+# engine's staging and the K_HIST extension all take it from here)
+LE_MAX = 64
+
+
+def logit_edit_reference(bits, vocab: int, ids, vals, spans) -> np.ndarray:
+    """The twin of ``csrc/kernels/logit_edit_kernels.h``, which holds the
+    contract, bit for bit: rows of bf16 bit patterns ``bits`` (uint16 [R][ld],
+    columns ``vocab .. ld`` padding) under the flat lists ``ids`` (int32 [N])
+    and ``vals`` (float32 [N]) and the per-row ``spans`` [R][4] = (allow_off,
+    n_allow, bias_off, n_bias); returns the edited copy.  An offset is clamped
+    into [0, N], a count into [0, min(LE_MAX, N - offset)].  With an allow
+    list every column < ``vocab`` outside it becomes 0xff80; then each bias
+    entry whose id is in [0, vocab), the first of its id, adds its value in
+    float32 (one rounding) and rounds to bf16 by nearest-even."""
+    out = np.array(bits, dtype=np.uint16)
+    out = out.reshape(1, -1) if out.ndim == 1 else out
+    V = int(vocab)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    vals = np.asarray(vals, dtype=np.float32).reshape(-1)
+    N = min(len(ids), len(vals))
+    spans = np.asarray(spans, dtype=np.int64).reshape(-1, 4)
+    for r in range(out.shape[0]):
+        a_off, n_a, b_off, n_b = (int(x) for x in spans[r])
+        a_off, b_off = min(max(a_off, 0), N), min(max(b_off, 0), N)
+        n_a = min(max(n_a, 0), LE_MAX, N - a_off)
+        n_b = min(max(n_b, 0), LE_MAX, N - b_off)
+        if n_a > 0:
+            al = ids[a_off:a_off + n_a]
+            mask = np.ones(V, dtype=bool)
+            mask[al[(al >= 0) & (al < V)]] = False
+            out[r, :V][mask] = 0xFF80
+        seen = set()
+        for i in range(n_b):
+            t = int(ids[b_off + i])
+            if not 0 <= t < V or t in seen:
+                continue
+            seen.add(t)
+            with np.errstate(all="ignore"):
+                x = np.float32(bf16_values(out[r, t:t + 1])[0] + vals[b_off + i])
+            out[r, t] = bf16_bits(np.array([x], dtype=np.float32))[0]
+    return out

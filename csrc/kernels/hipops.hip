@@ -836,6 +836,7 @@ PYBIND11_MODULE(_hipops, m) {
   m.def("sample_truncated", &sample_truncated, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"),
         py::arg("inv_temp"), py::arg("keys"), py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("stream"),
         py::arg("log_min_p") = 0);
+  m.attr("ST_MAX_BLOCKS") = (int)ST_MAX_BLOCKS;
   m.def("logprobs", &logprobs, py::arg("logits"), py::arg("R"), py::arg("V"), py::arg("ld"), py::arg("tok"),
         py::arg("out_lp"), py::arg("out_id"), py::arg("stream"));
   m.attr("LP_TOP") = (int)LP_TOP;

@@ -24,6 +24,7 @@
 #include "penalty_kernels.h"
 #include "sample_truncate_kernels.h"
 #include "skinny_kernels.h"
+#include "stop_kernels.h"
 #include "summarise_kernels.h"
 #include "text_kernels.h"
 
@@ -504,6 +505,30 @@ static void history_record(uintptr_t hist, int n_slots, int stride, uintptr_t to
   check_launch();
 }
 
+// out[r] = the lowest stop entry of row r that equals the tail of its generated tokens, the step's token tok[r]
+// included, or -1: stop_kernels.h holds the contract.  hist int32 [n_slots][stride] (0: no row reads a history, every
+// row's slot must then be outside the table, which the kernel treats as such), rows int32 [R][STOP_ROW_WORDS], ent
+// int32 [N][STOP_ENT_WORDS].  One wave a row, four rows a block, grid-stride above STOP_MAX_BLOCKS.
+static void stop_match(uintptr_t tok, int R, uintptr_t hist, int n_slots, int stride, uintptr_t rows, uintptr_t ent,
+                       int N, uintptr_t out, uintptr_t stream) {
+  const char* fn = "stop_match";
+  require_in(fn, R >= 0 && N >= 0, "needs R, N >= 0");
+  require_in(fn, hist == 0 ? (n_slots == 0 && stride == 0) : (n_slots > 0 && stride > 0),
+             "needs a history table of n_slots, stride > 0, or none and 0, 0");
+  require_in(fn, (int64_t)n_slots * stride < (int64_t)1 << 31, "history table too large");
+  require_in(fn, (int64_t)R * STOP_ROW_WORDS < (int64_t)1 << 31 && (int64_t)N * STOP_ENT_WORDS < (int64_t)1 << 31,
+             "too many rows or entries");
+  require_in(fn, tok != 0 && rows != 0 && out != 0 && (N == 0 || ent != 0), "null pointer");
+  require_in(fn, tok % 4 == 0 && hist % 4 == 0 && rows % 4 == 0 && ent % 4 == 0 && out % 4 == 0,
+             "arrays must be 4-byte aligned");
+  if (R == 0) return;
+  constexpr int per = STOP_THREADS / 64;
+  hipLaunchKernelGGL(stop_match_kernel, dim3(std::min((R + per - 1) / per, (int)STOP_MAX_BLOCKS)), dim3(STOP_THREADS),
+                     0, S(stream), P<const int32_t>(tok), R, P<const int32_t>(hist), n_slots, stride,
+                     P<const int32_t>(rows), P<const int32_t>(ent), N, P<int32_t>(out));
+  check_launch();
+}
+
 static void row_rms(uintptr_t x, uintptr_t r, int T, int D, float eps, uintptr_t stream) {
   require(T >= 0 && D > 0 && D % 512 == 0, "row_rms expects D % 512 == 0");
   require(x % 16 == 0 && r % 4 == 0, "row_rms: misaligned pointers");
@@ -853,6 +878,13 @@ PYBIND11_MODULE(_hipops, m) {
         py::arg("vals"), py::arg("N"), py::arg("spans"), py::arg("stream"));
   m.attr("LE_MAX") = (int)LE_MAX;
   m.attr("LE_MAX_BLOCKS") = (int)LE_MAX_BLOCKS;
+  m.def("stop_match", &stop_match, py::arg("tok"), py::arg("R"), py::arg("hist"), py::arg("n_slots"), py::arg("stride"),
+        py::arg("rows"), py::arg("ent"), py::arg("N"), py::arg("out"), py::arg("stream"));
+  m.attr("STOP_ENTRIES") = (int)STOP_ENTRIES;
+  m.attr("STOP_LEN") = (int)STOP_LEN;
+  m.attr("STOP_ROW_WORDS") = (int)STOP_ROW_WORDS;
+  m.attr("STOP_ENT_WORDS") = (int)STOP_ENT_WORDS;
+  m.attr("STOP_MAX_BLOCKS") = (int)STOP_MAX_BLOCKS;
   m.def("row_rms", &row_rms);
   m.attr("GEMM_EPI_STORE") = (int)GM_EPI_STORE;
   m.attr("GEMM_EPI_SWIGLU") = (int)GM_EPI_SWIGLU;

@@ -39,6 +39,7 @@ from ..models.message import (ConversationNotFound, Message, MessageStatus,
                               PriorityParseError, eligibility_from_metadata, format_time,
                               level_priority_from_name, logprobs_from_metadata,
                               parse_priority, penalties_from_metadata, priority_name, sampling_from_metadata,
+                              stop_from_metadata,
                               truncation_from_metadata)
 from ..scheduler.resource_scheduler import Resource, ResourceError
 from ..utils.metrics import CONTENT_TYPE_LATEST
@@ -257,6 +258,8 @@ def create_app(gw_app, allowed_origins: Optional[List[str]] = None,
             logprobs_from_metadata(m.metadata)
             penalties_from_metadata(m.metadata)
             eligibility_from_metadata(m.metadata)
+            gw = getattr(G, "gateway", None)
+            stop_from_metadata(m.metadata, int(getattr(gw, "gen_tokens", 0) or G.cfg.backend.gen_tokens))
         except (ValueError, PriorityParseError, TypeError) as e:
             return _err(400, f"Invalid message format: {e}")
         bad = await _enqueue(m)

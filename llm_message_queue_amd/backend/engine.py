@@ -10,7 +10,9 @@ and returns immediately.  The pipeline is fully asynchronous:
     host never waits for token values;
   * completions are deterministic (greedy decode always yields a token), so
     a request's slot is freed at launch of its last step and can be re-admitted
-    into the NEXT step (same-stream ordering keeps its KV rows safe);
+    into the NEXT step (same-stream ordering keeps its KV rows safe) -- except
+    a request ended by a stop token or stop sequence, which is known only
+    when its step is reaped and completes there (``_reap_stops``);
   * at most ``max_inflight`` (2) steps are queued on the GPU; ``finish`` reaps
     finished steps (blocking only when the queue is full), so host work of the
     next tick overlaps the current forward and the GPU never idles between
@@ -40,7 +42,8 @@ import torch
 
 from ..models.llama_stub import LlamaConfig, LlamaStub
 from ..ops.gemm import SKINNY_CHUNKED_MAX_M, row_scale_len
-from ..ops.sampling import LE_MAX, LP_TOP, PEN_HIST_MAX, inv_temperature, min_p_log, row_keys
+from ..ops.sampling import (LE_MAX, LP_TOP, PEN_HIST_MAX, STOP_ENT_WORDS, STOP_ENTRIES, STOP_LEN, STOP_ROW_WORDS,
+                            inv_temperature, min_p_log, row_keys)
 
 
 @dataclass
@@ -110,6 +113,22 @@ class Request:
     min_p: float = 0.0
     logit_bias: Optional[Tuple[np.ndarray, np.ndarray]] = None
     allowed: Optional[np.ndarray] = None
+    # when to stop (``csrc/kernels/stop_kernels.h``).  ``max_tokens`` (0: the
+    # configured count) caps ``gen_tokens`` at admission; ``stop`` is the
+    # request's stop entries, each a sequence of 1..8 token ids (a stop token
+    # is an entry of one), compared with the tail of what this attempt has
+    # generated after every token; a match that would end the generation with
+    # fewer than ``min_tokens`` tokens is ignored.  None of them changes a
+    # token.  ``finish`` asks for the outcome to be reported; the engine sets
+    # ``finish_reason`` ("stop" / "length") and, for a stop, ``stop_entry``
+    # (the matched entry's index) with ``generated`` when the request completes
+    max_tokens: int = 0
+    min_tokens: int = 0
+    stop: Optional[list] = None
+    finish: bool = False
+    finish_reason: str = ""
+    stop_entry: int = -1
+    seq_key: int = 0              # its slot's admission key (unique per admission: names this attempt to queued steps)
 
 
 @dataclass
@@ -175,6 +194,9 @@ class _Inflight:
     host_out: object = None       # pinned int32 [>= S]: the sampled ids, copied back behind the forward
     lp_rows: object = None        # int64 [L]: the sampled rows scored by ``logprob_head`` (None: none)
     host_lp: object = None        # pinned (float32 [>= L][6], int32 [>= L][5]): their results, copied back likewise
+    stop_rows: object = None      # int64 [R]: the sampled rows that have stop entries (None: none)
+    host_stop: object = None      # pinned int32 [>= R]: their matched entry (-1: none), copied back likewise
+    stop_reqs: object = None      # (their requests, their slots' admission keys), as the launch saw them
 
 
 class BackendEngine:
@@ -361,6 +383,21 @@ class BackendEngine:
         self.s_minp = np.full(n_all, -np.inf, dtype=np.float32)
         self._eligibility_seen = False                      # a request has named min_p, an allow-list or a bias
         self.edited_steps = 0                               # forwards that edited a row by such a list (``logit_edit``)
+        # stop tokens and sequences (``stop_kernels.h``): the slot's entry
+        # table ``h_stop[s]`` (int32 [STOP_ENTRIES][1 + STOP_LEN], allocated
+        # with the first request that has one), how many entries, ``min_tokens``
+        # and whether an entry is longer than one token (its slot's tokens are
+        # then recorded in ``d_hist``)
+        self.s_stop = np.zeros(n_all, dtype=bool)
+        self.s_shist = np.zeros(n_all, dtype=bool)
+        self.s_nstop = np.zeros(n_all, dtype=np.int32)
+        self.s_mintok = np.zeros(n_all, dtype=np.int32)
+        self.s_stopkey = np.full(n_all, -1 << 62, dtype=np.int64)   # admission key of the request last stopped in the slot
+        self.h_stop = None
+        self._stop_pins = self._stop_pins_m = None          # the steps' stop results, copied back behind the ids
+        self.stopped_total = 0                              # requests ended by a stop
+        self.stop_steps = 0                                 # forwards that ran ``stop_match``
+        self.stop_dropped_rows = 0                          # decode rows computed after their request's stop
         # host copy of every scored token's log-probability and alternatives,
         # per slot, next to ``h_tokens`` (allocated with the first request that asks)
         self.h_lp = self.h_top_ids = self.h_top_lp = None
@@ -404,8 +441,10 @@ class BackendEngine:
         # (+ a sampling step's 1 / T and two key words per sampled row, padded to whole 256-row tiles,
         #  row index, top_k and top_p of its truncating rows, and the row index of a step's
         #  log-probability rows, and a penalised step's block: 10 words per penalised row and the token
-        #  rows to record, and an edited step's block: 6 words per row and its two lists, ids and values)
-        self._pins = [self._alloc_pin(4 * (8 * self.token_budget + (22 + 4 * LE_MAX) * slots + 64
+        #  rows to record, and an edited step's block: 6 words per row and its two lists, ids and values,
+        #  and a stop step's block: 7 words per row and its entries)
+        stop_words = 1 + STOP_ROW_WORDS + STOP_ENTRIES * STOP_ENT_WORDS
+        self._pins = [self._alloc_pin(4 * (8 * self.token_budget + (22 + 4 * LE_MAX + stop_words) * slots + 64
                                            + 3 * row_scale_len(slots) + 4))
                       for _ in range(ring)]
         # sampled token ids copied back behind each forward (read at reap)
@@ -430,7 +469,7 @@ class BackendEngine:
             # behind the copies still queued from it)
             self._pins_m = [self._alloc_pin(4 * (12 * self.micro_budget + 2 * self.micro_slots + 64
                                                  + 3 * row_scale_len(self.micro_slots)
-                                                 + (20 + 4 * LE_MAX) * self.micro_slots + 4))
+                                                 + (20 + 4 * LE_MAX + stop_words) * self.micro_slots + 4))
                             for _ in range(mr)]
             self._out_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32) for _ in range(mr)]
             self._lp_pins_m = [self._alloc_lp_pin(self.micro_slots) for _ in range(mr)]
@@ -630,6 +669,8 @@ class BackendEngine:
                 if self.micro:
                     continue                                  # (a later realtime request may still fit)
                 break
+            if r.max_tokens > 0:
+                r.gen_tokens = min(int(r.gen_tokens), int(r.max_tokens))   # (the request's own count from here on)
             if r.gen_tokens < 1:
                 r.gen_tokens = 1
             plen = max(1, min(len(r.prompt), cap - r.gen_tokens + 1))
@@ -641,6 +682,8 @@ class BackendEngine:
             r.aborted = False
             r.out_tokens = None
             r.out_logprobs = r.out_top_ids = r.out_top_logprobs = None
+            r.finish_reason = ""
+            r.stop_entry = -1
             base = 0
             s = self.conv_lru.pop(r.conv, None) if (r.conv >= 0 and not micro) else None
             if micro:
@@ -745,7 +788,32 @@ class BackendEngine:
                     self.h_evals[s, na:na + nb] = bv
                     self.s_ecnt[s] = (na, nb)
                     self.s_edit[s] = True
-            if self.s_pen[s] and self.d_hist is None:
+            # stop entries, greedy slots too: at most STOP_ENTRIES of 1..STOP_LEN
+            # tokens (any other is dropped); an id that fits no int32 is outside
+            # every vocabulary and never matches
+            if self.h_stop is not None:
+                self.s_stop[s] = self.s_shist[s] = False
+            if r.stop and self.runs_model:
+                ent = [np.asarray(e, dtype=np.int64).reshape(-1) for e in r.stop]
+                ent = [e for e in ent if 1 <= len(e) <= STOP_LEN][:STOP_ENTRIES]
+                if ent:
+                    if self.h_stop is None:
+                        self.h_stop = np.zeros((self.n_all, STOP_ENTRIES, STOP_ENT_WORDS), dtype=np.int32)
+                        ring = max(2, self.max_inflight)
+                        self._stop_pins = [self._alloc_pin(4 * self.n_all).view(torch.int32) for _ in range(ring)]
+                        if self.micro:
+                            self._stop_pins_m = [self._alloc_pin(4 * self.micro_slots).view(torch.int32)
+                                                 for _ in range(self.micro_inflight + 1)]
+                    tab = self.h_stop[s]
+                    tab[:] = 0
+                    for i, e in enumerate(ent):
+                        tab[i, 0] = len(e)
+                        tab[i, 1:1 + len(e)] = np.where((e >= 0) & (e < 1 << 31), e, -1)
+                    self.s_nstop[s] = len(ent)
+                    self.s_mintok[s] = min(max(int(r.min_tokens), 0), int(r.gen_tokens))
+                    self.s_stop[s] = True
+                    self.s_shist[s] = bool((tab[:len(ent), 0] > 1).any())
+            if (self.s_pen[s] or (self.h_stop is not None and self.s_shist[s])) and self.d_hist is None:
                 # the device-side token history, indexed [slot][absolute
                 # position] (``penalty_kernels.h``).  Not filled: a fill would
                 # be queued on this call's stream and nothing orders it with
@@ -758,6 +826,7 @@ class BackendEngine:
                 self.d_hist = torch.empty((self.n_all, self.max_ctx), dtype=torch.int32, device=self.device)
             # prefill order key: realtime-lane tiers sort before everything else
             self.s_seq[s] = self._admit_seq - (1 << 48 if 0 <= r.tier < self.fast_tiers else 0)
+            r.seq_key = int(self.s_seq[s])
             self._admit_seq += 1
             self.s_active[s] = True
             self.s_tier[s] = r.tier
@@ -1177,8 +1246,21 @@ class BackendEngine:
         # in the device history, and their sampled rows are drawn again on
         # their own path (``penalised_head``), greedy rows first.  Eager in the
         # micro pool as well.  A row that also truncates leaves ``trunc``
-        qrows = np.flatnonzero(self.s_pen[slot]) if self.d_hist is not None else np.zeros(0, dtype=np.int64)
+        # (and so are the token rows of slots that hold a stop entry longer
+        # than one token: ``stop_match`` reads their generated tokens there)
+        if self.d_hist is None:
+            qrows = np.zeros(0, dtype=np.int64)
+        elif self.h_stop is not None:
+            qrows = np.flatnonzero(self.s_pen[slot] | self.s_shist[slot])
+        else:
+            qrows = np.flatnonzero(self.s_pen[slot])
         Q = len(qrows)
+        # sampled rows with stop entries: compared after the head's last
+        # overwrite (``stop_match``), the result read when the step is reaped.
+        # Eager in the micro pool as well.  ``max_tokens`` alone needs none of it
+        srows = np.flatnonzero(self.s_stop[samp_slots]) if (self.h_stop is not None and S) \
+            else np.zeros(0, dtype=np.int64)
+        RS = len(srows)
         # Slots with an allow-list or a logit bias take the same path, their
         # penalty off (a span whose slot is -1: no history is read, and none
         # is recorded for them)
@@ -1195,7 +1277,7 @@ class BackendEngine:
             n_greedy = int(P - hot.sum())
             prows = np.concatenate([prows[~hot], prows[hot]])
         if micro and self._mg and n_pre == 0 and D == T and self._prev_out_m is not None and not sampling and not L \
-                and not Q and not P:
+                and not Q and not P and not RS:
             Tb = next((b for b in self.MICRO_GRAPH_BUCKETS if b >= T and b in self._mg), 0)
             if Tb:
                 return self._launch_micro_graph(Tb, t0, t_mono, pos, slot, samp_slots, dec_src)
@@ -1241,7 +1323,30 @@ class BackendEngine:
                 en = ec.sum(axis=1)
                 N = int(en.sum())
             E = P if (N or (pm > -np.inf).any()) else 0
-        buf = np.empty(o_edt + 5 * E + 2 * N, dtype=np.int32)
+        # the stop block behind that (empty when no sampled row has an entry):
+        # per row its index and record (slot, gen_from, end, min_tokens,
+        # ent_off, n_ent), then the rows' entries, packed
+        o_stp = o_edt + 5 * E + 2 * N
+        NS = 0
+        if RS:
+            st_slots = samp_slots[srows]
+            st_cnt = self.s_nstop[st_slots].astype(np.int64)
+            NS = int(st_cnt.sum())
+        buf = np.empty(o_stp + (1 + STOP_ROW_WORDS) * RS + STOP_ENT_WORDS * NS, dtype=np.int32)
+        if RS:
+            st_off = np.cumsum(st_cnt) - st_cnt
+            buf[o_stp:o_stp + RS] = srows
+            o_ent = o_stp + (1 + STOP_ROW_WORDS) * RS
+            rec = buf[o_stp + RS:o_ent].reshape(RS, STOP_ROW_WORDS)
+            rec[:, 0] = np.where(self.s_shist[st_slots], st_slots, -1)
+            rec[:, 1] = self.s_plen[st_slots]
+            rec[:, 2] = self.s_plen[st_slots] + self.s_gen[st_slots]
+            rec[:, 3] = self.s_mintok[st_slots]
+            rec[:, 4] = st_off
+            rec[:, 5] = st_cnt
+            # (the rows' first ``st_cnt`` entries, row by row: the order the offsets count)
+            buf[o_ent:].reshape(NS, STOP_ENT_WORDS)[:] = \
+                self.h_stop[st_slots][np.arange(STOP_ENTRIES)[None, :] < st_cnt[:, None]]
         if Q:
             buf[o_pen + 10 * P:o_edt] = qrows
         if E:
@@ -1293,6 +1398,9 @@ class BackendEngine:
         sid = self.micro_id if micro else self.step_id
         pins, outs = (self._pins_m, self._out_pins_m) if micro else (self._pins, self._out_pins)
         host_lp = (self._lp_pins_m if micro else self._lp_pins)[sid % len(pins)] if L else None
+        host_stop = (self._stop_pins_m if micro else self._stop_pins)[sid % len(pins)] if RS else None
+        # (the requests of those rows and their slots' admission keys, as this launch sees them)
+        stop_reqs = ([self.active[x] for x in st_slots.tolist()], self.s_seq[st_slots]) if RS else None
         k = sid % len(pins)
         pin = pins[k]
         if pin.numel() < nbytes:
@@ -1339,10 +1447,17 @@ class BackendEngine:
                                    d[o_edt:o_edt + E].view(torch.float32))
                     self.edited_steps += int(N > 0)
                 self.penalised_steps += int(P > 0)
+            if RS:
+                skw["stop"] = (self.d_hist, None, d[o_stp:o_stp + RS].long(),
+                               d[o_stp + RS:o_ent].view(RS, STOP_ROW_WORDS), d[o_ent:].view(NS, STOP_ENT_WORDS))
+                self.stop_steps += 1
             ev0 = self._start_event()
             te = time.perf_counter_ns()
             fwd = self._micro_forward if micro else self.model.forward
             out = fwd(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til, n_dec=D, **skw)
+            if RS:
+                out, flags = out[:-1], out[-1]
+                out = out[0] if len(out) == 1 else out
             if L:
                 out, lp, ids = out
             self.host_ns[2] += time.perf_counter_ns() - te
@@ -1353,12 +1468,16 @@ class BackendEngine:
             if L:
                 host_lp[0][:L].copy_(lp, non_blocking=True)
                 host_lp[1][:L].copy_(ids, non_blocking=True)
+            if RS:
+                host_stop[:RS].copy_(flags, non_blocking=True)
             ev = self._end_event(T, ev0 is not None)
         return self._retire(sid, T, n_pre, n_dec, S, samp_slots, out, host_out, ev, ev0, t0, t_mono, micro,
-                            lp_rows=lrows if L else None, host_lp=host_lp)
+                            lp_rows=lrows if L else None, host_lp=host_lp, stop_rows=srows if RS else None,
+                            host_stop=host_stop, stop_reqs=stop_reqs)
 
     def _retire(self, sid: int, T: int, n_pre: int, n_dec: int, S: int, ss, out, host_out, ev, ev0,
-                t0: float, t_mono: int, micro: bool, graph: bool = False, lp_rows=None, host_lp=None) -> bool:
+                t0: float, t_mono: int, micro: bool, graph: bool = False, lp_rows=None, host_lp=None,
+                stop_rows=None, host_stop=None, stop_reqs=None) -> bool:
         """The deterministic bookkeeping behind every enqueued forward (a
         serving step, an eager micro-forward or a graph replay): every sampled
         slot gets one token, finished requests leave their slots, and the
@@ -1373,27 +1492,12 @@ class BackendEngine:
         completed = []
         for x in done.tolist():
             r = self.active.pop(x)
-            r.prefilled = int(self.s_plen[x]) - r.reused
-            r.generated = int(self.s_gen[x])
             completed.append(r)
-            if micro:
-                # a micro slot never parks dialog KV (conv_lru holds serving slots only): always freed
-                self.s_conv[x] = -1
-                self.free_micro.append(x)
-            elif r.conv >= 0:
-                # park the dialog KV: every position but the last sampled token
-                self.s_cached[x] = self.s_plen[x] + self.s_gen[x] - 1
-                old = self.conv_lru.pop(r.conv, None)
-                if old is not None and old != x:           # a stale copy elsewhere: free it
-                    self.s_conv[old] = -1
-                    self.free.append(old)
-                self.conv_lru[r.conv] = x
-            else:
-                self.s_conv[x] = -1
-                self.free.append(x)
+            self._leave_slot(x, r, int(self.s_gen[x]))
         self.s_active[done] = False
         f = _Inflight(sid, ev, T, n_pre, n_dec, completed, firsts, t0, out, t_mono, ev0, micro=micro,
-                      samp_slots=ss, gidx=gidx, host_out=host_out, lp_rows=lp_rows, host_lp=host_lp)
+                      samp_slots=ss, gidx=gidx, host_out=host_out, lp_rows=lp_rows, host_lp=host_lp,
+                      stop_rows=stop_rows, host_stop=host_stop, stop_reqs=stop_reqs)
         if micro:
             self._prev_out_m = out
             self._qm.append(f)
@@ -1409,6 +1513,86 @@ class BackendEngine:
         self.completed_total += len(completed)
         self.completed_tokens += sum(len(r.prompt) + r.gen_tokens - 1 for r in completed)
         return True
+
+    def _leave_slot(self, x: int, r: Request, generated: int) -> None:
+        """Request ``r`` (already out of ``active``) completes in slot ``x``
+        after ``generated`` tokens: the slot is freed, or parked with the
+        dialog's KV."""
+        r.prefilled = int(self.s_plen[x]) - r.reused
+        r.generated = generated
+        if self.s_micro[x]:
+            # a micro slot never parks dialog KV (conv_lru holds serving slots only): always freed
+            self.s_conv[x] = -1
+            self.free_micro.append(x)
+        elif r.conv >= 0:
+            # park the dialog KV: every position but the last sampled token
+            self.s_cached[x] = self.s_plen[x] + generated - 1
+            old = self.conv_lru.pop(r.conv, None)
+            if old is not None and old != x:           # a stale copy elsewhere: free it
+                self.s_conv[old] = -1
+                self.free.append(old)
+            self.conv_lru[r.conv] = x
+        else:
+            self.s_conv[x] = -1
+            self.free.append(x)
+
+    def _reap_stops(self, f: _Inflight) -> None:
+        """Act on a reaped step's stop results.  The bookkeeping of a step is
+        decided at launch and a stop is known only now, up to ``max_inflight``
+        steps later, so for each row that matched an entry and whose request
+        has no stop recorded yet (steps of a pool are reaped in launch order:
+        the first match wins):
+          * the request still holds its slot: it completes here, into this
+            step's ``completed``, cut after the matched token.  The slot is
+            free (or parked) for the NEXT launch; steps already queued still
+            compute its rows -- their tokens are dropped here
+            (``stop_dropped_rows``) -- and stream order keeps a new occupant,
+            prefilled by a later step on the same stream, from reading
+            anything they write, exactly as ``_abort_slots`` argues.  Their
+            ids land in ``h_tokens`` rows of the slot before any id of the
+            new occupant does (reaps are FIFO), which rewrites every row it
+            reads;
+          * a later launch already completed it at its full length: that
+            step's reap delivers it, and its outputs are cut there to the
+            length recorded here (``r.generated``); the tokens counted at
+            that launch are corrected, and so is the parked context if the
+            slot is still parked as that request left it.  The gateway
+            admits a conversation's next turn only once the previous turn's
+            completion has been delivered -- it is reported by the later
+            step's reap, after this one -- so no next turn can have been
+            admitted in between; an engine-level caller that admits one
+            sooner is detected by the slot's admission key and keeps the
+            uncut context (every position of it was computed)."""
+        reqs, keys = f.stop_reqs
+        slots = f.samp_slots[f.stop_rows]
+        # rows of a request whose stop an earlier step recorded (admission keys
+        # are unique, so the slot's last stop is that of the row's own request)
+        late = self.s_stopkey[slots] == keys
+        self.stop_dropped_rows += int(late.sum())
+        flags = f.host_stop.numpy()[:len(reqs)]
+        for i in np.flatnonzero((flags >= 0) & ~late).tolist():
+            r = reqs[i]
+            if r.seq_key != int(keys[i]) or r.aborted:     # (an attempt that was aborted, or admitted again since)
+                continue
+            k, x = int(flags[i]), int(slots[i])
+            gi = int(f.gidx[f.stop_rows[i]])
+            r.finish_reason = "stop"
+            r.stop_entry = k
+            self.s_stopkey[x] = r.seq_key
+            self.stopped_total += 1
+            if self.active.get(x) is r:
+                del self.active[x]
+                self.s_active[x] = False
+                self._leave_slot(x, r, gi + 1)
+                f.completed.append(r)
+                self.completed_total += 1
+                self.completed_tokens += len(r.prompt) + gi
+            else:
+                self.completed_tokens -= r.generated - (gi + 1)
+                r.generated = gi + 1
+                if r.conv >= 0 and not self.s_micro[x] and self.conv_lru.get(r.conv) == x \
+                        and int(self.s_seq[x]) == r.seq_key and not self.s_active[x]:
+                    self.s_cached[x] = self.s_plen[x] + gi
 
     def _step_flops(self, T: int, S: int) -> int:
         """Matrix-multiply FLOPs of one forward of ``T`` tokens sampling ``S``
@@ -1524,11 +1708,15 @@ class BackendEngine:
                 self.h_lp[ss[rows], f.gidx[rows]] = lp[:, 0]
                 self.h_top_lp[ss[rows], f.gidx[rows]] = lp[:, 1:]
                 self.h_top_ids[ss[rows], f.gidx[rows]] = f.host_lp[1].numpy()[:len(keep)][keep]
+        if f.stop_reqs is not None:
+            self._reap_stops(f)
         for r in f.firsts:
             if not r.aborted:
                 r.first_token_ns = now
         for r in f.completed:
             r.done_ns = now
+            if not r.finish_reason:
+                r.finish_reason = "length"
             r.out_tokens = self.h_tokens[r.slot, :min(r.generated, self.max_ctx)].copy()
             if r.logprobs >= 0 and self.h_lp is not None:
                 n = len(r.out_tokens)

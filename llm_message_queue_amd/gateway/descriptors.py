@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from ..ops.sampling import LE_MAX as EXT_LIST_MAX, LP_TOP   # (entries an extension list; alternatives a row)
+from ..ops.sampling import STOP_ENTRIES, STOP_LEN
 
 # --------------------------------------------------------------------------- descriptors
 K_DISPATCH, K_DONE, K_FAIL = 1, 2, 3     # K_FAIL: an evacuating backend hands a request back
@@ -27,12 +28,15 @@ K_CANCEL = 7        # [kind, handle lo/hi, origin]: origin -> the GPU running it
 # the payload is the compressed-context prefix (N5 salient tokens) then the history
 K_HIST = 8
 # completion records (K_DONE) carry the turn's generated token ids in the
-# payload columns, their count in col 10 (dialog turns: the origin's history)
+# payload columns, their count in col 10 (dialog turns: the origin's history;
+# requests dispatched with FINISH: their ``generation`` record), and in col 11
+# how the generation ended (``pack_finish``; 0: not reported)
 DESC_HDR = 20       # [kind, handle lo/hi, origin, tier, arrival lo/hi, enq lo/hi, gen, plen, flags, conv lo/hi,
 #                    dialog history length, decision - enq (us), processing timeout (ms),
 #                    sampling temperature (float32 bits), sampling seed lo/hi];
 #                    tier = tier | presence, frequency, repetition penalties << 4 (``pack_penalties``)
-#                           | EXTENSION; gen = gen | min_p permille << 16 (``pack_gen``);
+#                           | EXTENSION; gen = the request's own count (the configured one, or its ``max_tokens``)
+#                           | min_p permille << 16 (``pack_gen``) | FINISH;
 #                    flags = (home GPU + 1) | KV_MIGRATE | DIALOG_TURN | top_k << 10 | top_p permille << 20
 #                            | LOGPROBS
 KV_MIGRATE = 1 << 8     # descriptor flag: hold the turn until its KV arrives from the home GPU
@@ -114,8 +118,71 @@ def unpack_gen(col: int) -> tuple:
     c = int(col)
     if c < 0:
         return c, 0.0
-    pm = c >> MIN_P_SHIFT
+    pm = (c >> MIN_P_SHIFT) & 0x3FF
     return c & GEN_MASK, (pm / 1000.0 if pm <= 1000 else 0.0)
+
+
+# bit 26 of col 9 (above min_p's 10 bits): the request named a stop key
+# (``max_tokens``, ``min_tokens``, ``stop_token_ids``, ``stop_sequences``) -- the
+# serving GPU sends its generated ids home in its K_DONE payload, as a dialog
+# turn's, and how it ended in col 11
+FINISH = 1 << 26
+FIN_LENGTH, FIN_STOP = 1, 2     # col 11 of a K_DONE row: 0 none, 1 "length", 2 + the matched entry's index "stop"
+
+
+def pack_finish(finish_reason: str, stop_entry: int = -1) -> int:
+    """Col 11 of a K_DONE row."""
+    if finish_reason == "stop" and 0 <= int(stop_entry) < STOP_ENTRIES:
+        return FIN_STOP + int(stop_entry)
+    return FIN_LENGTH if finish_reason in ("length", "stop") else 0
+
+
+def unpack_finish(col: int) -> tuple:
+    """``(finish_reason, stop_entry)`` of a K_DONE row's col 11 (``("", -1)``:
+    not reported)."""
+    c = int(col)
+    if FIN_STOP <= c < FIN_STOP + STOP_ENTRIES:
+        return "stop", c - FIN_STOP
+    return ("length", -1) if c == FIN_LENGTH else ("", -1)
+
+
+def pack_stop_section(ext, min_tokens: int, entries) -> np.ndarray:
+    """The extension stream ``ext`` (``pack_extension`` words, possibly none)
+    with the stop section behind it: ``[n_entries, min_tokens, the entries'
+    lengths..., their tokens...]``.  A request without entries gets ``ext``
+    back unchanged (``min_tokens`` filters stops and means nothing without
+    one); one without lists gets the two zero counts of empty first sections
+    in front."""
+    ents = [np.asarray(e, dtype=np.int32).reshape(-1) for e in (entries or ())]
+    ents = [e for e in ents if 1 <= len(e) <= STOP_LEN][:STOP_ENTRIES]
+    ext = np.asarray(ext, dtype=np.int32).reshape(-1)
+    if not ents:
+        return ext
+    head = ext if len(ext) else np.zeros(2, dtype=np.int32)
+    return np.concatenate([head, [len(ents), max(0, int(min_tokens))], [len(e) for e in ents]] + ents).astype(np.int32)
+
+
+def unpack_stop_section(words) -> tuple:
+    """``(min_tokens, entries)`` of the stop section behind the first two
+    sections of an extension stream (``(0, [])``: none); counts and lengths
+    that leave the stream or their ranges end the list there."""
+    w = np.asarray(words, dtype=np.int32).reshape(-1)
+    if not len(w):
+        return 0, []
+    na = min(max(int(w[0]), 0), EXT_LIST_MAX, len(w) - 1)
+    rest = w[1 + na:]
+    nb = min(max(int(rest[0]), 0), EXT_LIST_MAX, (len(rest) - 1) // 2) if len(rest) else 0
+    st = rest[1 + 2 * nb:]
+    if len(st) < 2:
+        return 0, []
+    n = min(max(int(st[0]), 0), STOP_ENTRIES, len(st) - 2)
+    lens, toks, out = st[2:2 + n].tolist(), st[2 + n:], []
+    for ln in lens:
+        if not 1 <= ln <= STOP_LEN or ln > len(toks):
+            break
+        out.append(toks[:ln].copy())
+        toks = toks[ln:]
+    return max(0, int(st[1])), out
 
 
 

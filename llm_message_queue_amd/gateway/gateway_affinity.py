@@ -23,7 +23,7 @@ from .descriptors import conv_key
 
 
 class AffinityMixin:
-    def _remember_dialog(self, m: Message, gpu: int, tokens=None) -> None:
+    def _remember_dialog(self, m: Message, gpu: int, tokens=None, generated: int = 0) -> None:
         """Completion of a conversation turn: its home GPU (KV residency) and
         the dialog tokens a non-resident replay needs -- exactly what the
         home GPU's parked KV holds for the turn: its prompt (as the engine
@@ -31,7 +31,9 @@ class AffinityMixin:
         ``tokens``: the turn's generated ids, read back with the step that
         sampled them (``Request.out_tokens``; carried in the K_DONE record
         when another GPU ran it).  Without them (a backend that keeps no ids)
-        placeholders keep the replay's cost right."""
+        placeholders keep the replay's cost right.  ``generated``: how many
+        tokens the turn generated where that is not the configured count (its
+        own ``max_tokens``, or a stop: the parked KV ends there too)."""
         cid = m.conversation_id
         if not cid:
             return
@@ -42,7 +44,7 @@ class AffinityMixin:
         if not len(p):
             p = np.zeros(1, dtype=np.int32)                   # (the engine's stand-in for an empty prompt)
         h = self.conv_hist.get(cid)
-        g = max(0, self.gen_tokens - 1)
+        g = max(0, (int(generated) if 0 < generated <= self.gen_tokens else self.gen_tokens) - 1)
         real = tokens is not None and len(tokens) >= g
         gen = np.asarray(tokens, dtype=np.int32)[:g] if real else np.zeros(g, dtype=np.int32)
         self.counters["dialog_ids_real" if real else "dialog_ids_placeholder"] += 1

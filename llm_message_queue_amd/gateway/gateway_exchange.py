@@ -32,6 +32,7 @@ from .descriptors import (DESC_HDR, DIALOG_TURN, EXTENSION, FAIL_UNTOUCHED, K_CA
                           fill_logprob_row, logprob_chunks, pack_logprob_stream, pack_penalties, pack_truncation,
                           take_logprob_rows, unpack_penalties,
                           pack_extension, pack_gen, unpack_extension, unpack_gen,
+                          FINISH, pack_stop_section, unpack_finish, unpack_stop_section,
                           unpack_logprob_stream, unpack_truncation)
 
 _NO_EXT = np.zeros(0, dtype=np.int32)
@@ -207,11 +208,17 @@ class ExchangeMixin:
                     # a dialog turn's generated ids ride in its K_DONE record's payload (not in the
                     # K_LOGP records queued ahead of it under the same handle)
                     for k, (h, kind) in enumerate(zip(a[:, 0].tolist(), a[:, 4].tolist())):
-                        t = toks.pop(h, None) if kind == K_DONE else None
-                        if t is not None:
+                        item = toks.pop(h, None) if kind == K_DONE else None
+                        if item is not None:
+                            t, fin = item
+                            # (a row carries ``cap`` = prompt_cap ids: where a request generates more, its
+                            #  origin sees the first ``cap`` of them, in a dialog's history as in the
+                            #  ``generation`` record of a request that named a stop key -- configure
+                            #  prompt_cap >= gen_tokens for those to equal a local run's)
                             n = min(len(t), cap)
                             d[k, 10] = n
                             d[k, DESC_HDR:DESC_HDR + n] = np.asarray(t[:n], dtype=np.int32)
+                            d[k, 11] = fin
                 for k in np.flatnonzero(a[:, 4] == K_LOGP).tolist():
                     # (handle, offset, words, words in all, K_LOGP): a chunk of a log-probability stream
                     h, off, n, total = a[k, :4].tolist()
@@ -387,12 +394,18 @@ class ExchangeMixin:
             small[k, 4] = min(0x7FFFFFFF, max(0, (m.popped_ns - m.enqueued_at) // 1000)) \
                 if (m.popped_ns and m.enqueued_at) else 0
             small[k, 5] = min(0x7FFFFFFF, self._timeout_ns(m) // 1_000_000)
-            temp[k], seed[k], top_k, top_p, logprobs, pens, (min_p, bias, allowed) = self._sampling(m)
+            temp[k], seed[k], top_k, top_p, logprobs, pens, (min_p, bias, allowed), (max_tok, min_tok, stops, fin) = \
+                self._sampling(m, self.gen_tokens)
             small[k, 2] |= pack_truncation(top_k, top_p) | (LOGPROBS if logprobs >= 0 else 0)
             ext = pack_extension(allowed, *bias) if (m.tier >= 0 and (len(allowed) or len(bias[0]))) else _NO_EXT
+            if stops and m.tier >= 0:
+                # the stop lists and ``min_tokens``: one more section behind the two lists (``max_tokens`` rides
+                # in col 9 and ``min_tokens`` means nothing without a stop: neither alone makes a request wait)
+                ext = pack_stop_section(ext, min_tok, stops)
             if m.tier >= 0:
                 small[k, 0] |= pack_penalties(*pens) | (EXTENSION if len(ext) else 0)
-            gens[k] = pack_gen(self.gen_tokens, min_p) if min_p else self.gen_tokens
+            gen = max_tok or self.gen_tokens                  # (the request's own count)
+            gens[k] = (pack_gen(gen, min_p) if min_p else gen) | (FINISH if fin else 0)
             ctx.append((hist, pre, ext))
         buf[:, 0] = K_DISPATCH
         _put64(buf, 1, v[:, 0])
@@ -479,6 +492,8 @@ class ExchangeMixin:
                 al, bi, bv = unpack_extension(buf[pl + hl:])
                 r.allowed = al if len(al) else None
                 r.logit_bias = (bi, bv) if len(bi) else None
+                r.min_tokens, st = unpack_stop_section(buf[pl + hl:])
+                r.stop = st or None
             if self._await_hist.pop((src, h), None) is not None:
                 ready.append(r)
         return ready
@@ -507,6 +522,7 @@ class ExchangeMixin:
                 rows[:, 4].tolist(), rows[:, 9].tolist(), rows[:, 10].tolist(), rows[:, 14].tolist(),
                 rows[:, 16].tolist(), rows[:, 11].tolist())):
             self._next_req += 1
+            fin = gen > 0 and bool(gen & FINISH)
             hl, pl = hv & mask, hv >> HIST_LEN_BITS
             top_k, top_p = unpack_truncation(fl)
             tier, pres, freq, rep = unpack_penalties(tier)
@@ -522,7 +538,7 @@ class ExchangeMixin:
                                timeout_ns=int(to_ms) * 1_000_000, dialog=bool(fl & DIALOG_TURN),
                                temperature=temps[k], seed=seeds[k], top_k=top_k, top_p=top_p,
                                logprobs=LP_TOP if fl & LOGPROBS else -1, presence_penalty=pres,
-                               frequency_penalty=freq, repetition_penalty=rep, min_p=min_p))
+                               frequency_penalty=freq, repetition_penalty=rep, min_p=min_p, finish=fin))
         return out
 
     def _owe_logprobs(self, origin: int, handle: int, r: Request) -> None:
@@ -537,9 +553,9 @@ class ExchangeMixin:
 
     def _remote_done_rows(self, rows: np.ndarray) -> None:
         """K_DONE rows: my requests another GPU finished."""
-        for k, (h, gpu, adm, done, nt) in enumerate(zip(
+        for k, (h, gpu, adm, done, nt, fin) in enumerate(zip(
                 _get64(rows, 1).tolist(), rows[:, 3].tolist(), _get64(rows, 5).tolist(), _get64(rows, 7).tolist(),
-                rows[:, 10].tolist())):
+                rows[:, 10].tolist(), rows[:, 11].tolist())):
             lp = self._lp_parts.pop((int(gpu), h), None)
             m = self.remote_out.pop(h, None)
             if m is None:
@@ -547,8 +563,11 @@ class ExchangeMixin:
             self.inflight_by_tier[m.tier] -= 1
             if lp is not None and not self.table.cancelled(m):
                 self._attach_generation(m, *unpack_logprob_stream(lp))
+            if fin and not self.table.cancelled(m):
+                self._attach_finish(m, rows[k, DESC_HDR:DESC_HDR + max(nt, 0)], *unpack_finish(fin))
             if self.table.cancelled(m):       # cancelled after that GPU launched its last token
                 self._finish_cancel(m, done - adm, dispatched=True)
                 continue
-            self._remember_dialog(m, int(gpu), rows[k, DESC_HDR:DESC_HDR + nt] if nt > 0 else None)
+            self._remember_dialog(m, int(gpu), rows[k, DESC_HDR:DESC_HDR + nt] if nt > 0 else None,
+                                  int(nt) if fin else 0)
             self._complete(m, done - adm)     # (releases the balancer's gpu<j> endpoint with this RT)

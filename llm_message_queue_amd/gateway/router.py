@@ -32,9 +32,11 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..backend.engine import BackendEngine, Request
-from ..models.message import (PENALTY_KEYS, Message, MessageStatus, SamplingParseError, allowed_from_metadata,
-                              generation_record, logit_bias_from_metadata, logprobs_from_metadata,
-                              min_p_from_metadata, penalty_from_metadata,
+from ..models.message import (PENALTY_KEYS, STOP_KEYS, Message, MessageStatus, SamplingParseError, allowed_from_metadata,
+                              finish_record, generation_record, logit_bias_from_metadata, logprobs_from_metadata,
+                              max_tokens_from_metadata, min_p_from_metadata, min_tokens_from_metadata,
+                              penalty_from_metadata, stop_entries, stop_sequences_from_metadata,
+                              stop_token_ids_from_metadata,
                               priority_name, sampling_from_metadata, truncation_from_metadata)
 from ..parallel import planner
 from ..parallel.comm import Comm, SoloComm
@@ -45,7 +47,7 @@ from ..utils.logging import get_logger
 NS = 1_000_000_000
 
 from .descriptors import (DESC_HDR, FAIL_UNTOUCHED, GEN_MASK, K_CANCEL, K_CANCELLED, K_DISPATCH, K_DONE,  # noqa: F401
-                          K_FAIL, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, _get64, _put64, conv_key)
+                          K_FAIL, K_MIGRATE, K_TIMEOUT, KV_MIGRATE, _get64, _put64, conv_key, pack_finish)
 from .latency import (PATHS, P_LANE, P_OWN, P_PLAN_LOCAL, P_PLAN_REMOTE, STAGES, LatencyRecorder,  # noqa: F401
                       StageRecorder, _hbin, hist_percentile)
 from .gateway_admission import OwnAdmissionMixin
@@ -170,8 +172,9 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         self.foreign: Dict[int, Tuple[int, int, int]] = {}  # my engine req id -> (origin, handle, tier)
         self._done_owed: Dict[int, List[Tuple[int, int, int, int]]] = {r: [] for r in range(self.world)}
         self._done_pub: List[int] = [0] * self.world      # records of _done_owed announced this tick
-        # generated ids of the dialog turns in _done_owed (origin -> handle -> ids)
-        self._done_tok: Dict[int, Dict[int, np.ndarray]] = {r: {} for r in range(self.world)}
+        # generated ids of the dialog turns, and of the requests that named a stop key, in _done_owed
+        # (origin -> handle -> (ids, the K_DONE row's finish column))
+        self._done_tok: Dict[int, Dict[int, tuple]] = {r: {} for r in range(self.world)}
         # log-probability streams of the K_LOGP rows in _done_owed (origin -> handle -> int32 stream),
         # and the chunks received for my own requests ((source, handle) -> stream so far)
         self._done_lp: Dict[int, Dict[int, np.ndarray]] = {r: {} for r in range(self.world)}
@@ -457,20 +460,24 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             if len(prompt) else np.zeros(1, dtype=np.int32)
         ck = conv_key(m.conversation_id) if self.kv_residency else -1
         hist, pre = self._dialog_context(m)
-        temp, seed, top_k, top_p, logprobs, pens, (min_p, bias, allowed) = self._sampling(m)
-        return Request(req_id=m.handle, prompt=p, gen_tokens=self.gen_tokens, tier=tier, meta=m, conv=ck,
+        temp, seed, top_k, top_p, logprobs, pens, (min_p, bias, allowed), (max_tokens, min_tokens, stops, finish) = \
+            self._sampling(m, self.gen_tokens)
+        return Request(req_id=m.handle, prompt=p, gen_tokens=max_tokens or self.gen_tokens, tier=tier, meta=m, conv=ck,
+                       min_tokens=min_tokens, stop=stops or None, finish=finish,
                        history=hist, prefix=pre, timeout_ns=self._timeout_ns(m), temperature=temp, seed=seed,
                        top_k=top_k, top_p=top_p, logprobs=logprobs, presence_penalty=pens[0],
                        frequency_penalty=pens[1], repetition_penalty=pens[2], min_p=min_p,
                        logit_bias=bias if len(bias[0]) else None, allowed=allowed if len(allowed) else None)
 
+    _NO_STOP = (0, 0, [], False)
     _NO_ELIGIBILITY = (0.0, (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32)), np.zeros(0, dtype=np.int32))
 
     @staticmethod
-    def _sampling(m: Message) -> Tuple[float, int, int, float, int, Tuple[float, float, float], tuple]:
+    def _sampling(m: Message, gen_tokens: int = 0) -> tuple:
         """The message's effective ``(temperature, seed, top_k, top_p,
         logprobs, (presence, frequency, repetition penalty), (min_p,
-        (logit_bias ids, values), allowed_token_ids))``
+        (logit_bias ids, values), allowed_token_ids), (max_tokens, min_tokens,
+        stop entries, finish))``
         (``metadata.sampling``), lenient: this path also serves
         messages no route validated (the native ingress), so a bad
         temperature or seed falls back to greedy, a bad ``top_k`` / ``top_p``
@@ -486,11 +493,18 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
         ``allowed_token_ids`` only where they are in effect (greedy or not),
         and ``logprobs`` only where the message named it, so a
         message that named none of them keeps exactly ``{"temperature",
-        "seed"}``."""
+        "seed"}``.  The stop keys (``models.message.stop_from_metadata``;
+        ``gen_tokens`` is the configured count, the cap of ``max_tokens``):
+        a bad ``max_tokens``, ``min_tokens``, ``stop_token_ids`` or
+        ``stop_sequences`` turns that key off and leaves the others in effect
+        (the two lists both, where only their total is too long); ``max_tokens`` is 0 where the configured count holds.
+        Written back: ``max_tokens`` where named, ``min_tokens`` where above
+        0, the lists where not empty.  ``finish``: one of them is in effect,
+        so the message gets a ``finish_reason``."""
         md = m.metadata
         if not md or "sampling" not in md:
             # greedy (the default traffic): the seed is never read
-            return 0.0, 0, 0, 1.0, -1, (0.0, 0.0, 1.0), Gateway._NO_ELIGIBILITY
+            return 0.0, 0, 0, 1.0, -1, (0.0, 0.0, 1.0), Gateway._NO_ELIGIBILITY, Gateway._NO_STOP
         try:
             temp, seed = sampling_from_metadata(md, m.id)
         except SamplingParseError as e:
@@ -540,8 +554,60 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
             eff["logit_bias"] = {str(int(t)): float(v) for t, v in zip(*bias)}
         if len(allowed):
             eff["allowed_token_ids"] = [int(t) for t in allowed]
+        stop = Gateway._NO_STOP
+        sp = md["sampling"]
+        if isinstance(sp, dict) and any(k in sp for k in STOP_KEYS):
+            def lenient(parse, off):
+                try:
+                    return parse()
+                except SamplingParseError as e:
+                    md["sampling_error"] = "; ".join(x for x in (md.get("sampling_error"), str(e)) if x)
+                    return off
+
+            mx = lenient(lambda: max_tokens_from_metadata(md, gen_tokens), 0)
+            # each list on its own: a bad one leaves the other in effect; both off where only their total is too long
+            st = lenient(lambda: stop_token_ids_from_metadata(md), [])
+            sq = lenient(lambda: stop_sequences_from_metadata(md), [])
+            ent = lenient(lambda: stop_entries(st, sq), [])
+            mn = lenient(lambda: min_tokens_from_metadata(md, mx or gen_tokens), 0)   # (against the effective max_tokens)
+            n_tok = len(st) if ent else 0
+            if mx > 0:
+                eff["max_tokens"] = mx
+            if mn > 0:
+                eff["min_tokens"] = mn
+            if n_tok:
+                eff["stop_token_ids"] = [int(e[0]) for e in ent[:n_tok]]
+            if len(ent) > n_tok:
+                eff["stop_sequences"] = [[int(t) for t in e] for e in ent[n_tok:]]
+            stop = (mx, mn, ent, bool(mx > 0 or mn > 0 or ent))
         md["sampling"] = eff
-        return temp, seed, top_k, top_p, logprobs, tuple(pens), (min_p, bias, allowed)
+        return temp, seed, top_k, top_p, logprobs, tuple(pens), (min_p, bias, allowed), stop
+
+    @staticmethod
+    def _attach_finish(m: Message, tokens, finish_reason: str, stop_entry: int) -> None:
+        """``finish_reason`` (and ``stop_reason``, the matched entry: an int
+        for a stop token, a list for a sequence) into ``metadata.generation``
+        of a message that named a stop key, next to the log-probability
+        fields where the message asked for those too (cut to the same
+        length), else with the generated tokens alone."""
+        if tokens is None or not finish_reason or not isinstance(m.metadata, dict):
+            return
+        sp = m.metadata.get("sampling")
+        reason = None
+        if finish_reason == "stop" and isinstance(sp, dict) and stop_entry >= 0:
+            st, sq = sp.get("stop_token_ids") or [], sp.get("stop_sequences") or []
+            reason = st[stop_entry] if stop_entry < len(st) else \
+                (list(sq[stop_entry - len(st)]) if stop_entry - len(st) < len(sq) else None)
+        rec = finish_record(tokens, finish_reason, reason)
+        gen = m.metadata.get("generation")
+        if isinstance(gen, dict) and "token_logprobs" in gen:
+            n = len(rec["tokens"])
+            for k in ("tokens", "token_logprobs", "top_logprobs"):
+                if k in gen:
+                    gen[k] = gen[k][:n]
+            gen.update({k: v for k, v in rec.items() if k != "tokens"})
+        else:
+            m.metadata["generation"] = rec
 
     @staticmethod
     def _attach_generation(m: Message, tokens, lp, top_ids, top_lp) -> None:
@@ -736,17 +802,22 @@ class Gateway(ExchangeMixin, FailureMixin, AffinityMixin, ResourceMixin, OwnAdmi
                 if self.table.cancelled(m):     # cancelled after its last token was launched
                     self._finish_cancel(m, r.done_ns - r.admitted_ns, dispatched=True)
                     continue
-                self._remember_dialog(m, self.rank, r.out_tokens)
+                self._remember_dialog(m, self.rank, r.out_tokens, int(getattr(r, "generated", 0)))
                 self._attach_generation(m, r.out_tokens, getattr(r, "out_logprobs", None),
                                         getattr(r, "out_top_ids", None), getattr(r, "out_top_logprobs", None))
+                if getattr(r, "finish", False) and getattr(self.engine, "runs_model", False):
+                    self._attach_finish(m, r.out_tokens, r.finish_reason, r.stop_entry)
                 self._complete(m, r.done_ns - r.admitted_ns)
             else:
                 origin, handle, tier = self.foreign.pop(r.req_id)
                 if getattr(r, "out_logprobs", None) is not None and r.out_tokens is not None:
                     self._owe_logprobs(origin, handle, r)     # (ahead of the K_DONE: FIFO)
                 self._done_owed[origin].append((handle, tier, r.admitted_ns, r.done_ns, K_DONE))
-                if (r.conv >= 0 or r.dialog) and r.out_tokens is not None:   # a dialog turn: its ids go home
-                    self._done_tok[origin][handle] = r.out_tokens
+                fin = getattr(r, "finish", False) and getattr(self.engine, "runs_model", False)
+                # a dialog turn, or a request that named a stop key: its ids go home
+                if (r.conv >= 0 or r.dialog or fin) and r.out_tokens is not None:
+                    self._done_tok[origin][handle] = (r.out_tokens,
+                                                      pack_finish(r.finish_reason, r.stop_entry) if fin else 0)
 
     def tick(self, pump=None):
         """One serving tick, pipelined so host work overlaps the forward:

@@ -250,7 +250,8 @@ class LlamaStub:
     def forward(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 sample_idx: torch.Tensor, tiles: Optional[torch.Tensor] = None, n_dec: int = 0,
                 small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
-                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None, logp=None, pen=None):
+                keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None, logp=None, pen=None,
+                stop=None):
         """One step over T tokens; returns greedy next-token ids for the rows
         in ``sample_idx`` (the last token of each request's chunk).  With
         ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
@@ -283,6 +284,17 @@ class LlamaStub:
         ``min_p``; rows with only those have a penalty span whose slot is -1,
         and ``hist`` is None where no slot has a penalty (nothing is recorded
         or read then).
+        ``stop`` = (hist int32 [slots][max_ctx] or None, rec int32 [Q] or None,
+        rows int64 [R] into the sampled rows, records int32 [R][6], ent int32
+        [N][9]): the sampled rows that have stop tokens or stop sequences
+        (``csrc/kernels/stop_kernels.h``).  ``rec`` names token rows to record
+        in ``hist`` where ``pen`` does not already (the engine merges them
+        into ``pen``'s list: the slots that hold an entry longer than one
+        token).  After the last overwrite of the tokens ``ops.stop_match``
+        compares each such row's generated tokens with its entries, and its
+        int32 [R] result (the matched entry, -1: none) is returned behind the
+        tokens, and behind ``lp, ids`` where ``logp`` is given too.  No token
+        is changed by it.
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -295,6 +307,8 @@ class LlamaStub:
         the FP8 weights (``hidden``); the head stays bf16."""
         if pen is not None and pen[0] is not None and pen[1].numel():
             self.ops.history_record(pen[0], tokens, pos, slot, pen[1])
+        if stop is not None and stop[0] is not None and stop[1] is not None and stop[1].numel():
+            self.ops.history_record(stop[0], tokens, pos, slot, stop[1])
         if self.prune_last and self.residual_in_gemm:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus,
                               quant=quant)
@@ -327,10 +341,13 @@ class LlamaStub:
             out.index_copy_(0, rows, self.ops.penalised_head(
                 sel.index_select(0, rows), self.lm_head, it, kk, top_k, top_p, hist, spans, params,
                 n_greedy=n_greedy, **kw))
+        flags = None
+        if stop is not None:
+            flags = self.ops.stop_match(out.index_select(0, stop[2]), stop[0], stop[3], stop[4])
         if logp is None:
-            return out
+            return out if stop is None else (out, flags)
         lp, ids = self.ops.logprob_head(sel.index_select(0, logp), self.lm_head, out.index_select(0, logp))
-        return out, lp, ids
+        return (out, lp, ids) if stop is None else (out, lp, ids, flags)
 
     @torch.no_grad()
     def hidden(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,

@@ -528,6 +528,118 @@ def eligibility_from_metadata(md: Any) -> tuple:
     return min_p_from_metadata(md), logit_bias_from_metadata(md), allowed_from_metadata(md)
 
 
+from ..ops.sampling import STOP_ENTRIES, STOP_LEN  # noqa: E402  (entries a request, tokens an entry: the stop kernel's)
+STOP_KEYS = ("max_tokens", "min_tokens", "stop_token_ids", "stop_sequences")
+
+
+def _count(sp, key: str, lo: int, hi, default: int) -> int:
+    if sp is None or key not in sp:
+        return default
+    v = sp[key]
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        raise SamplingParseError(f"sampling.{key} must be an integer in [{lo}, {hi}]" if hi is not None
+                                 else f"sampling.{key} must be an integer, at least {lo}")
+    return int(v)
+
+
+def max_tokens_from_metadata(md: Any, gen_tokens: int = 0) -> int:
+    """``max_tokens`` of a message's ``metadata.sampling`` object: an integer
+    in [1, ``gen_tokens``], the configured count (``backend.gen_tokens``),
+    which stays the default and the cap; 0 where the key is absent.  With
+    ``gen_tokens`` 0 (the caller knows no configured count) any integer >= 1
+    passes.  Raises ``SamplingParseError`` on anything else."""
+    return _count(_sampling_object(md), "max_tokens", 1, int(gen_tokens) if gen_tokens > 0 else None, 0)
+
+
+def min_tokens_from_metadata(md: Any, cap: int = 0) -> int:
+    """``min_tokens`` of a message's ``metadata.sampling`` object: an integer
+    in [0, ``cap``] (the request's ``max_tokens``, else the configured count;
+    0: no cap known), default 0.  Raises ``SamplingParseError`` on anything
+    else."""
+    return _count(_sampling_object(md), "min_tokens", 0, int(cap) if cap > 0 else None, 0)
+
+
+def stop_token_ids_from_metadata(md: Any) -> list:
+    """``stop_token_ids`` of a message's ``metadata.sampling`` object: a list
+    of 1..8 distinct token ids in [0, 2^31), in the order given; empty where
+    the key is absent.  Raises ``SamplingParseError`` on anything else."""
+    sp = _sampling_object(md)
+    if sp is None or "stop_token_ids" not in sp:
+        return []
+    st = sp["stop_token_ids"]
+    if not isinstance(st, (list, tuple)) or not (1 <= len(st) <= STOP_ENTRIES):
+        raise SamplingParseError(f"sampling.stop_token_ids must be a list of 1 to {STOP_ENTRIES} token ids")
+    ids = [_token_id(x, "stop_token_ids") for x in st]
+    if len(set(ids)) != len(ids):
+        raise SamplingParseError("sampling.stop_token_ids must be distinct")
+    return ids
+
+
+def stop_sequences_from_metadata(md: Any) -> list:
+    """``stop_sequences`` of a message's ``metadata.sampling`` object: a list
+    of 1..8 lists of 1..8 token ids in [0, 2^31) each; empty where the key is
+    absent.  Raises ``SamplingParseError`` on anything else."""
+    sp = _sampling_object(md)
+    if sp is None or "stop_sequences" not in sp:
+        return []
+    sq = sp["stop_sequences"]
+    if not isinstance(sq, (list, tuple)) or not (1 <= len(sq) <= STOP_ENTRIES):
+        raise SamplingParseError(f"sampling.stop_sequences must be a list of 1 to {STOP_ENTRIES} lists")
+    out = []
+    for e in sq:
+        if not isinstance(e, (list, tuple)) or not (1 <= len(e) <= STOP_LEN):
+            raise SamplingParseError(f"sampling.stop_sequences entries must be lists of 1 to {STOP_LEN} token ids")
+        out.append([_token_id(x, "stop_sequences") for x in e])
+    return out
+
+
+def stop_entries(stop_token_ids: list, stop_sequences: list) -> list:
+    """The stop entries in entry order: the stop tokens in the order given,
+    each an entry of one token, then the sequences; at most 8 together, else
+    ``SamplingParseError``."""
+    out = [[t] for t in stop_token_ids] + list(stop_sequences)
+    if len(out) > STOP_ENTRIES:
+        raise SamplingParseError(f"sampling.stop_token_ids and stop_sequences hold at most {STOP_ENTRIES} "
+                                 "entries together")
+    return out
+
+
+def stop_entries_from_metadata(md: Any) -> list:
+    """The stop entries of a message's ``metadata.sampling`` object
+    (:func:`stop_token_ids_from_metadata`, :func:`stop_sequences_from_metadata`,
+    :func:`stop_entries`).  Raises ``SamplingParseError`` on a bad value."""
+    return stop_entries(stop_token_ids_from_metadata(md), stop_sequences_from_metadata(md))
+
+
+def stop_from_metadata(md: Any, gen_tokens: int = 0) -> tuple:
+    """``(max_tokens, min_tokens, entries, n_stop_tokens)`` of a message's
+    ``metadata.sampling`` object (:func:`max_tokens_from_metadata`,
+    :func:`stop_entries_from_metadata`; the first ``n_stop_tokens`` entries
+    are its ``stop_token_ids``).  ``min_tokens``: an integer in [0,
+    ``max_tokens``] (the configured count where ``max_tokens`` is absent),
+    default 0 -- a stop that would end the generation with fewer tokens is
+    ignored.  It filters the stop decision; it masks no logit, and none of
+    the four keys changes a token that is drawn.  Raises
+    ``SamplingParseError`` on anything else."""
+    sp = _sampling_object(md)
+    mx = max_tokens_from_metadata(md, gen_tokens)
+    mn = min_tokens_from_metadata(md, mx or gen_tokens)
+    ent = stop_entries_from_metadata(md)
+    n_tok = len(sp["stop_token_ids"]) if (sp is not None and "stop_token_ids" in sp) else 0
+    return mx, mn, ent, n_tok
+
+
+def finish_record(tokens, finish_reason: str, stop_reason=None) -> Dict[str, Any]:
+    """``metadata.generation`` of a completed message that named a stop key
+    (``max_tokens``, ``min_tokens``, ``stop_token_ids``, ``stop_sequences``):
+    the generated tokens, ``finish_reason`` ("stop" or "length") and, for a
+    stop, the matched entry (an int for a stop token, a list for a sequence)."""
+    out = {"tokens": [int(t) for t in tokens], "finish_reason": str(finish_reason)}
+    if finish_reason == "stop" and stop_reason is not None:
+        out["stop_reason"] = stop_reason
+    return out
+
+
 def generation_record(tokens, token_logprobs, top_ids, top_logprobs, n: int) -> Dict[str, Any]:
     """``metadata.generation`` of a completed message that asked for
     ``logprobs = n``: the generated tokens, their log-probabilities and, for

@@ -865,6 +865,40 @@ def logit_edit(logits: torch.Tensor, ids: torch.Tensor, vals: torch.Tensor, span
     return logits
 
 
+from .sampling import STOP_ENT_WORDS, STOP_ROW_WORDS  # noqa: E402  (words a row record / an entry)
+
+
+def stop_match(tok: torch.Tensor, hist, rows: torch.Tensor, ent: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """Per row the lowest stop entry that equals the tail of its generated
+    tokens, the step's token ``tok[r]`` included, or -1 -> int32 [R]
+    (``csrc/kernels/stop_kernels.h`` holds the contract, ``ops.sampling.
+    stop_match_reference`` is its exact twin).  ``tok`` int32 [R]; ``hist``
+    int32 [slots][stride], the device-side token history, or None where no
+    row reads one; ``rows`` int32 [>= R][6] = (slot, gen_from, end,
+    min_tokens, ent_off, n_ent); ``ent`` int32 [N][9] = (length, tokens oldest
+    first)."""
+    if tok.dtype != torch.int32 or tok.dim() != 1 or not tok.is_cuda or not tok.is_contiguous():
+        raise ValueError("stop_match: tok must be contiguous int32 [R] on a GPU")
+    R = tok.numel()
+    if hist is not None:
+        _pen_hist("stop_match", hist, tok.device)
+    for t, n, w in ((rows, "rows", STOP_ROW_WORDS), (ent, "ent", STOP_ENT_WORDS)):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != w or not t.is_contiguous() or t.device != tok.device:
+            raise ValueError(f"stop_match: {n} must be contiguous int32 [n][{w}] on tok's device")
+    if rows.shape[0] < R:
+        raise ValueError("stop_match: rows must hold a record for every row of tok")
+    y = out if out is not None else torch.empty(R, dtype=torch.int32, device=tok.device)
+    if y.dtype != torch.int32 or y.dim() != 1 or y.numel() < R or not y.is_contiguous() or y.device != tok.device:
+        raise ValueError("stop_match: out must be contiguous int32 [>= R] on tok's device")
+    if R:
+        _native.require_hipops().stop_match(tok.data_ptr(), R, hist.data_ptr() if hist is not None else 0,
+                                            hist.shape[0] if hist is not None else 0,
+                                            hist.shape[1] if hist is not None else 0, rows.data_ptr(),
+                                            ent.data_ptr() if ent.numel() else 0, ent.shape[0], y.data_ptr(),
+                                            torch.cuda.current_stream(tok.device).cuda_stream)
+    return y[:R]
+
+
 def sample_bits(keys: torch.Tensor, n0: int, count: int) -> torch.Tensor:
     """The device noise generator's bits (int32 [n_keys][count], the uint32
     bit patterns) of columns ``n0 .. n0 + count`` under ``keys`` [n][2]."""

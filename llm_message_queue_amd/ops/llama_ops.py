@@ -218,6 +218,13 @@ class HipOps:
         from . import gemm as G
         G.history_record(hist, tok.contiguous(), pos.contiguous(), slot.contiguous(), rows.contiguous())
 
+    def stop_match(self, tok, hist, rows, ent):
+        """Per row the lowest stop entry that ends its generated tokens, the
+        step's token ``tok`` (int32 [R]) included, or -1 -> int32 [R]
+        (``ops.gemm.stop_match``; ``csrc/kernels/stop_kernels.h``)."""
+        from . import gemm as G
+        return G.stop_match(tok.to(torch.int32).contiguous(), hist, rows.contiguous(), ent.contiguous())
+
     def mlp_up(self, x: torch.Tensor, w_gu: torch.Tensor, fused: bool, min_fused_tokens: int) -> torch.Tensor:
         """silu(x·Wgᵀ) * (x·Wuᵀ).  ``fused``: ``w_gu`` is in swiglu order and
         steps of >= ``min_fused_tokens`` rows run the hand-written GEMM with
@@ -424,6 +431,13 @@ class RefOps:
         """Reference of ``HipOps.history_record``."""
         r = rows.long()
         hist[slot.long()[r], pos.long()[r]] = tok[r].to(hist.dtype)
+
+    def stop_match(self, tok, hist, rows, ent):
+        """Reference of ``HipOps.stop_match``: the numpy twin."""
+        from .sampling import stop_match_reference
+        return torch.from_numpy(stop_match_reference(
+            tok.cpu().numpy(), None if hist is None else hist.cpu().numpy(), rows.cpu().numpy(),
+            ent.cpu().numpy())).to(tok.device)
 
     def mlp_up(self, x, w_gu, fused: bool, min_fused_tokens: int):
         """Reference of ``HipOps.mlp_up`` (``w_gu`` in swiglu order if fused)."""

@@ -395,3 +395,59 @@ def logit_edit_reference(bits, vocab: int, ids, vals, spans) -> np.ndarray:
                 x = np.float32(bf16_values(out[r, t:t + 1])[0] + vals[b_off + i])
             out[r, t] = bf16_bits(np.array([x], dtype=np.float32))[0]
     return out
+
+
+# the package's one copy of csrc/kernels/stop_kernels.h's constants (the parser's caps, the engine's staging and the
+# extension stream all take them from here)
+STOP_ENTRIES = 8
+STOP_LEN = 8
+STOP_ROW_WORDS = 6
+STOP_ENT_WORDS = 1 + STOP_LEN
+
+
+def stop_table(entries) -> np.ndarray:
+    """Stop entries (sequences of token ids, each of 1..STOP_LEN) as rows of
+    the packed entry table int32 [n][STOP_ENT_WORDS] = (length, the tokens,
+    oldest first, zero padded)."""
+    out = np.zeros((len(entries), STOP_ENT_WORDS), dtype=np.int32)
+    for i, e in enumerate(entries):
+        e = np.asarray(e, dtype=np.int64).reshape(-1)
+        if not 1 <= len(e) <= STOP_LEN:
+            raise ValueError(f"a stop entry holds 1..{STOP_LEN} tokens")
+        out[i, 0] = len(e)
+        out[i, 1:1 + len(e)] = np.where((e >= 0) & (e < 1 << 31), e, -1)
+    return out
+
+
+def stop_match_reference(tok, hist, rows, ent) -> np.ndarray:
+    """The twin of ``csrc/kernels/stop_kernels.h``, which holds the contract
+    (all integer: exact): int32 [R], per row the lowest stop entry that equals
+    the tail of ``hist[slot][gen_from:end] + [tok[r]]``, or -1.  ``tok`` int32
+    [R]; ``hist`` int32 [slots][stride] or None; ``rows`` int32 [R][6] =
+    (slot, gen_from, end, min_tokens, ent_off, n_ent); ``ent`` int32
+    [N][1 + STOP_LEN] = (length, tokens oldest first).  Spans and entry ranges
+    are clamped as the kernel clamps them; a slot outside the table leaves
+    only ``tok[r]`` to compare; an entry whose length is outside 1..STOP_LEN
+    is ignored."""
+    tok = np.asarray(tok, dtype=np.int32).reshape(-1)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, STOP_ROW_WORDS)
+    ent = np.asarray(ent, dtype=np.int32).reshape(-1, STOP_ENT_WORDS)
+    N = len(ent)
+    n_slots, stride = (0, 0) if hist is None else np.asarray(hist).shape
+    out = np.full(len(tok), -1, dtype=np.int32)
+    for r in range(len(tok)):
+        slot, a, b, min_tokens, off, cnt = (int(v) for v in rows[r])
+        a = min(max(a, 0), stride)
+        b = min(max(b, a), stride)
+        w = [int(x) for x in hist[slot][a:b]] if 0 <= slot < n_slots else []
+        w.append(int(tok[r]))
+        if len(w) < min_tokens:
+            continue
+        off = min(max(off, 0), N)
+        cnt = min(max(cnt, 0), STOP_ENTRIES, N - off)
+        for k in range(cnt):
+            n = int(ent[off + k, 0])
+            if 1 <= n <= STOP_LEN and n <= len(w) and w[len(w) - n:] == [int(x) for x in ent[off + k, 1:1 + n]]:
+                out[r] = k
+                break
+    return out

@@ -394,9 +394,10 @@ class LlamaStub:
         # SKINNY_PROJ_MAX_M rows; larger steps: the 256x256-tile kernel, split-K
         # (profiles/r6_skinny_chunked.jsonl)
         # (on a micro-forward's CU partition only up to SKINNY_MAX_M: there the
-        # split-K tiles were faster for larger steps)
+        # split-K tiles were faster for larger steps; only with the norm weight
+        # folded into wqkv, fused_qkv: the kernel applies the row scale alone)
         skinny = (small or nolib) and T <= (G.SKINNY_MAX_M if small else G.SKINNY_PROJ_MAX_M) \
-            and self.row_scale_norm and self.fused_mlp
+            and self.row_scale_norm and self.fused_mlp and self.fused_qkv
         sk_cus = small_cus if small else self._cus
         rows_qkv = self.fused_qkv and (T >= self.min_fused_qkv_tokens or small or nolib)
         qkv_split = {}

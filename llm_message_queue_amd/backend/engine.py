@@ -40,7 +40,7 @@ from typing import Deque, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..models.llama_stub import LlamaConfig, LlamaStub
+from ..models.llama_stub import LlamaConfig, LlamaStub, LogitEdit, Penalise, Stops, Truncate
 from ..ops.gemm import SKINNY_CHUNKED_MAX_M, row_scale_len
 from ..ops.sampling import (LE_MAX, LP_TOP, PEN_HIST_MAX, STOP_ENT_WORDS, STOP_ENTRIES, STOP_LEN, STOP_ROW_WORDS,
                             inv_temperature, min_p_log, row_keys)
@@ -164,6 +164,39 @@ class _NullCtx:
 
     def __exit__(self, *exc):
         return False
+
+
+class _Staging:
+    """The layout of one step's int32 staging buffer: the blocks in the
+    order given, each ``(name, words)`` or ``(name, words, align)`` -- a
+    block that is not empty starts on a multiple of ``align`` words, the
+    words skipped before it zero.  ``host`` and ``dev`` give the same block
+    of the host buffer (numpy) and of its device copy ``dbuf`` (torch), as
+    int32 or (``f32``) float32, in the shape asked for."""
+
+    def __init__(self, *blocks):
+        self.at = {}
+        n, pads = 0, []
+        for name, words, *align in blocks:
+            if words and align and n % align[0]:
+                pads.append((n, n + align[0] - n % align[0]))
+                n = pads[-1][1]
+            self.at[name] = (n, n + words)
+            n += words
+        self.buf = np.empty(n, dtype=np.int32)
+        for a, b in pads:
+            self.buf[a:b] = 0
+        self.dbuf = None
+
+    def host(self, name: str, shape=None, f32: bool = False) -> np.ndarray:
+        a, b = self.at[name]
+        v = self.buf[a:b].view(np.float32) if f32 else self.buf[a:b]
+        return v if shape is None else v.reshape(shape)
+
+    def dev(self, name: str, shape=None, f32: bool = False) -> torch.Tensor:
+        a, b = self.at[name]
+        v = self.dbuf[a:b].view(torch.float32) if f32 else self.dbuf[a:b]
+        return v if shape is None else v.view(shape)
 
 
 class BackendHung(Exception):
@@ -1281,16 +1314,8 @@ class BackendEngine:
             Tb = next((b for b in self.MICRO_GRAPH_BUCKETS if b >= T and b in self._mg), 0)
             if Tb:
                 return self._launch_micro_graph(Tb, t0, t_mono, pos, slot, samp_slots, dec_src)
-        o_dec = 3 * T + S
-        o_til = o_dec + 2 * D
-        # sampling rows: 1 / T (float32 bits) and the row keys of the S
-        # sampled rows behind the tiles, both whole 256-row tiles long and
-        # 16-byte aligned on the device (the epilogue's vector loads)
-        o_smp = (o_til + 4 * NT + 3) & ~3 if sampling else o_til + 4 * NT
         Sp = row_scale_len(S) if sampling else 0
-        # rows that also ask for top-k / top-p: their indices into the sampled
-        # rows, top_k and top_p (float32 bits) behind the keys, same copy
-        # (and, where one of them asks for min_p, every such row's log(min_p) behind them)
+        # rows that also ask for top-k / top-p / min_p (RM: one of them asks for min_p)
         if sampling:
             minp = self.s_minp[samp_slots]
             by_m = minp > -np.inf
@@ -1301,19 +1326,8 @@ class BackendEngine:
             trows = ()
         R = len(trows)
         RM = R if (R and by_m[trows].any()) else 0
-        o_trn = o_smp + 3 * Sp
-        # the log-probability rows behind the truncation block (nothing when
-        # there are none: the buffer is then what it is without the feature)
-        o_lgp = o_trn + 3 * R + RM
-        # the penalty block behind the log-probability rows (empty when
-        # unused): per penalised row its index, span (slot, from, split, end),
-        # parameters, top_k and top_p, then the token rows to record
-        o_pen = o_lgp + L
-        # the edit block behind that (empty unless a row of this step has an
-        # allow-list, a bias or, penalised, a min_p): per row log(min_p) and
-        # the span (allow_off, n_allow, bias_off, n_bias), then the N ids and
-        # the N values of the rows' lists
-        o_edt = o_pen + 10 * P + Q
+        # edited rows (E: one of the P rows has an allow-list, a bias or,
+        # penalised, a min_p; N: the words of their lists)
         E = N = 0
         if P:
             ps = samp_slots[prows]
@@ -1323,35 +1337,68 @@ class BackendEngine:
                 en = ec.sum(axis=1)
                 N = int(en.sum())
             E = P if (N or (pm > -np.inf).any()) else 0
-        # the stop block behind that (empty when no sampled row has an entry):
-        # per row its index and record (slot, gen_from, end, min_tokens,
-        # ent_off, n_ent), then the rows' entries, packed
-        o_stp = o_edt + 5 * E + 2 * N
         NS = 0
         if RS:
             st_slots = samp_slots[srows]
             st_cnt = self.s_nstop[st_slots].astype(np.int64)
             NS = int(st_cnt.sum())
-        buf = np.empty(o_stp + (1 + STOP_ROW_WORDS) * RS + STOP_ENT_WORDS * NS, dtype=np.int32)
-        if RS:
-            st_off = np.cumsum(st_cnt) - st_cnt
-            buf[o_stp:o_stp + RS] = srows
-            o_ent = o_stp + (1 + STOP_ROW_WORDS) * RS
-            rec = buf[o_stp + RS:o_ent].reshape(RS, STOP_ROW_WORDS)
-            rec[:, 0] = np.where(self.s_shist[st_slots], st_slots, -1)
-            rec[:, 1] = self.s_plen[st_slots]
-            rec[:, 2] = self.s_plen[st_slots] + self.s_gen[st_slots]
-            rec[:, 3] = self.s_mintok[st_slots]
-            rec[:, 4] = st_off
-            rec[:, 5] = st_cnt
-            # (the rows' first ``st_cnt`` entries, row by row: the order the offsets count)
-            buf[o_ent:].reshape(NS, STOP_ENT_WORDS)[:] = \
-                self.h_stop[st_slots][np.arange(STOP_ENTRIES)[None, :] < st_cnt[:, None]]
+        # the step's staging buffer, one copy to the device.  A block a step
+        # does not use is empty: the buffer is then what it is without the feature
+        lay = _Staging(
+            ("tok", T), ("pos", T), ("slot", T), ("samp", S), ("dec_rows", D), ("dec_src", D), ("tiles", 4 * NT),
+            # sampling rows: 1 / T and the row keys of the S sampled rows, both
+            # whole 256-row tiles long and 16-byte aligned on the device (the
+            # epilogue's vector loads)
+            ("inv_temp", Sp, 4), ("keys", 2 * Sp),
+            ("trunc_rows", R), ("trunc_k", R), ("trunc_p", R), ("trunc_minp", RM),
+            ("logp", L),
+            # per penalised row its index, span (slot, from, split, end),
+            # parameters, top_k and top_p, then the token rows to record
+            ("pen_rows", P), ("pen_spans", 4 * P), ("pen_params", 3 * P), ("pen_k", P), ("pen_p", P), ("record", Q),
+            # per edited row log(min_p) and the span (allow_off, n_allow,
+            # bias_off, n_bias), then the N ids and the N values of the rows' lists
+            ("edit_minp", E), ("edit_spans", 4 * E), ("edit_ids", N), ("edit_vals", N),
+            # per stop row its index and record (slot, gen_from, end,
+            # min_tokens, ent_off, n_ent), then the rows' entries, packed
+            ("stop_rows", RS), ("stop_records", STOP_ROW_WORDS * RS), ("stop_entries", STOP_ENT_WORDS * NS))
+        h = lay.host
+        h("tok")[:] = toks
+        h("pos")[:] = pos
+        h("slot")[:] = slot
+        h("samp")[:] = samp
+        h("dec_rows")[:] = dec_rows
+        h("dec_src")[:] = dec_src
+        h("tiles")[:] = tiles.reshape(-1)
+        if sampling:
+            it = h("inv_temp", f32=True)
+            it[:S] = inv_temperature(temp)
+            it[S:] = 0
+            kk = h("keys", (Sp, 2))
+            kk[:S] = row_keys(self.s_seed[samp_slots], self.s_gen[samp_slots]).view(np.int32)
+            kk[S:] = 0
+        if R:
+            h("trunc_rows")[:] = trows
+            h("trunc_k")[:] = self.s_topk[samp_slots[trows]]
+            h("trunc_p", f32=True)[:] = self.s_topp[samp_slots[trows]]
+            if RM:
+                h("trunc_minp", f32=True)[:] = minp[trows]
+        if L:
+            h("logp")[:] = lrows
+        if P:
+            h("pen_rows")[:] = prows
+            sp = h("pen_spans", (P, 4))
+            sp[:, 0] = np.where(self.s_pen[ps], ps, -1)
+            sp[:, 1] = self.s_pfrom[ps]
+            sp[:, 2] = self.s_plen[ps]
+            sp[:, 3] = self.s_plen[ps] + self.s_gen[ps]
+            h("pen_params", (P, 3), f32=True)[:] = self.s_penp[ps]
+            h("pen_k")[:] = self.s_topk[ps]
+            h("pen_p", f32=True)[:] = self.s_topp[ps]
         if Q:
-            buf[o_pen + 10 * P:o_edt] = qrows
+            h("record")[:] = qrows
         if E:
-            buf[o_edt:o_edt + E] = pm.view(np.int32)
-            es = buf[o_edt + E:o_edt + 5 * E].reshape(E, 4)
+            h("edit_minp", f32=True)[:] = pm
+            es = h("edit_spans", (E, 4))
             es[:] = 0
             if N:
                 off = np.cumsum(en) - en
@@ -1359,42 +1406,24 @@ class BackendEngine:
                 es[:, 1] = ec[:, 0]
                 es[:, 2] = off + ec[:, 0]
                 es[:, 3] = ec[:, 1]
-                o_ids = o_edt + 5 * E
+                e_ids, e_vals = h("edit_ids"), h("edit_vals", f32=True)
                 for i in np.flatnonzero(en):
-                    a, n = o_ids + int(off[i]), int(en[i])
-                    buf[a:a + n] = self.h_eids[ps[i], :n]
-                    buf[a + N:a + N + n] = self.h_evals[ps[i], :n].view(np.int32)
-        if P:
-            buf[o_pen:o_pen + P] = prows
-            sp = buf[o_pen + P:o_pen + 5 * P].reshape(P, 4)
-            sp[:, 0] = np.where(self.s_pen[ps], ps, -1)
-            sp[:, 1] = self.s_pfrom[ps]
-            sp[:, 2] = self.s_plen[ps]
-            sp[:, 3] = self.s_plen[ps] + self.s_gen[ps]
-            buf[o_pen + 5 * P:o_pen + 8 * P] = self.s_penp[ps].view(np.int32).reshape(-1)
-            buf[o_pen + 8 * P:o_pen + 9 * P] = self.s_topk[ps]
-            buf[o_pen + 9 * P:o_pen + 10 * P] = self.s_topp[ps].view(np.int32)
-        if R:
-            buf[o_trn:o_trn + R] = trows
-            buf[o_trn + R:o_trn + 2 * R] = self.s_topk[samp_slots[trows]]
-            buf[o_trn + 2 * R:o_trn + 3 * R] = self.s_topp[samp_slots[trows]].view(np.int32)
-            if RM:
-                buf[o_trn + 3 * R:o_lgp] = minp[trows].view(np.int32)
-        if L:
-            buf[o_lgp:o_pen] = lrows
-        if sampling:
-            buf[o_til + 4 * NT:o_trn] = 0
-            buf[o_smp:o_smp + S] = inv_temperature(temp).view(np.int32)
-            buf[o_smp + Sp:o_smp + Sp + 2 * S] = \
-                row_keys(self.s_seed[samp_slots], self.s_gen[samp_slots]).view(np.int32).reshape(-1)
-        buf[:T] = toks
-        buf[T:2 * T] = pos
-        buf[2 * T:3 * T] = slot
-        buf[3 * T:o_dec] = samp
-        buf[o_dec:o_dec + D] = dec_rows
-        buf[o_dec + D:o_til] = dec_src
-        buf[o_til:o_til + 4 * NT] = tiles.reshape(-1)
-        nbytes = buf.nbytes
+                    a, n = int(off[i]), int(en[i])
+                    e_ids[a:a + n] = self.h_eids[ps[i], :n]
+                    e_vals[a:a + n] = self.h_evals[ps[i], :n]
+        if RS:
+            h("stop_rows")[:] = srows
+            rec = h("stop_records", (RS, STOP_ROW_WORDS))
+            rec[:, 0] = np.where(self.s_shist[st_slots], st_slots, -1)
+            rec[:, 1] = self.s_plen[st_slots]
+            rec[:, 2] = self.s_plen[st_slots] + self.s_gen[st_slots]
+            rec[:, 3] = self.s_mintok[st_slots]
+            rec[:, 4] = np.cumsum(st_cnt) - st_cnt
+            rec[:, 5] = st_cnt
+            # (the rows' first ``st_cnt`` entries, row by row: the order the offsets count)
+            h("stop_entries", (NS, STOP_ENT_WORDS))[:] = \
+                self.h_stop[st_slots][np.arange(STOP_ENTRIES)[None, :] < st_cnt[:, None]]
+        nbytes = lay.buf.nbytes
         sid = self.micro_id if micro else self.step_id
         pins, outs = (self._pins_m, self._out_pins_m) if micro else (self._pins, self._out_pins)
         host_lp = (self._lp_pins_m if micro else self._lp_pins)[sid % len(pins)] if L else None
@@ -1405,61 +1434,48 @@ class BackendEngine:
         pin = pins[k]
         if pin.numel() < nbytes:
             pin = pins[k] = self._alloc_pin(2 * nbytes)
-        pin.numpy()[:nbytes] = buf.view(np.uint8)
+        pin.numpy()[:nbytes] = lay.buf.view(np.uint8)
         host_out = outs[k]
         prev = self._prev_out_m if micro else self._prev_out
         stream = self.rt_stream if micro else self.main_stream
         ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
         with ctx:
-            d = pin[:nbytes].to(dev, non_blocking=True).view(torch.int32)
-            tok_d = d[:T].long()
+            lay.dbuf = pin[:nbytes].to(dev, non_blocking=True).view(torch.int32)
+            d = lay.dev
+            tok_d = d("tok").long()
             if D:
                 if prev is None:
                     raise RuntimeError("decode token without a previous step output")
-                rows = d[o_dec:o_dec + D].long()
-                src = d[o_dec + D:o_til].long()
-                tok_d.index_copy_(0, rows, prev.index_select(0, src).long())
-            til = d[o_til:o_til + 4 * NT].view(NT, 4) if self.use_tiles else None
+                tok_d.index_copy_(0, d("dec_rows").long(), prev.index_select(0, d("dec_src").long()).long())
+            til = d("tiles", (NT, 4)) if self.use_tiles else None
             skw = {}
             if sampling:
-                skw = {"inv_temp": d[o_smp:o_smp + Sp].view(torch.float32),
-                       "keys": d[o_smp + Sp:o_smp + 3 * Sp].view(Sp, 2)}
+                skw = {"inv_temp": d("inv_temp", f32=True), "keys": d("keys", (Sp, 2))}
                 self.sampled_steps += 1
                 if R:
-                    skw["trunc"] = (d[o_trn:o_trn + R].long(), d[o_trn + R:o_trn + 2 * R],
-                                    d[o_trn + 2 * R:o_trn + 3 * R].view(torch.float32))
-                    if RM:
-                        skw["trunc"] += (d[o_trn + 3 * R:o_lgp].view(torch.float32),)
+                    skw["trunc"] = Truncate(d("trunc_rows").long(), d("trunc_k"), d("trunc_p", f32=True),
+                                            d("trunc_minp", f32=True) if RM else None)
                     self.truncated_steps += 1
             if L:
-                skw["logp"] = d[o_lgp:o_lgp + L].long()
+                skw["logp"] = d("logp").long()
                 self.logprob_steps += 1
             if Q or P:
-                skw["pen"] = (self.d_hist, d[o_pen + 10 * P:o_pen + 10 * P + Q], d[o_pen:o_pen + P].long(),
-                              d[o_pen + P:o_pen + 5 * P].view(P, 4),
-                              d[o_pen + 5 * P:o_pen + 8 * P].view(torch.float32).view(P, 3),
-                              d[o_pen + 8 * P:o_pen + 9 * P], d[o_pen + 9 * P:o_pen + 10 * P].view(torch.float32),
-                              n_greedy)
-                if E:
-                    o_ids = o_edt + 5 * E
-                    skw["pen"] += ((d[o_ids:o_ids + N], d[o_ids + N:o_ids + 2 * N].view(torch.float32),
-                                    d[o_edt + E:o_ids].view(E, 4)) if N else None,
-                                   d[o_edt:o_edt + E].view(torch.float32))
-                    self.edited_steps += int(N > 0)
+                ed = LogitEdit(d("edit_ids"), d("edit_vals", f32=True), d("edit_spans", (E, 4))) if N else None
+                skw["pen"] = Penalise(self.d_hist, d("record"), d("pen_rows").long(), d("pen_spans", (P, 4)),
+                                      d("pen_params", (P, 3), f32=True), d("pen_k"), d("pen_p", f32=True), n_greedy,
+                                      ed, d("edit_minp", f32=True) if E else None)
+                self.edited_steps += int(N > 0)
                 self.penalised_steps += int(P > 0)
             if RS:
-                skw["stop"] = (self.d_hist, None, d[o_stp:o_stp + RS].long(),
-                               d[o_stp + RS:o_ent].view(RS, STOP_ROW_WORDS), d[o_ent:].view(NS, STOP_ENT_WORDS))
+                skw["stop"] = Stops(self.d_hist, None, d("stop_rows").long(), d("stop_records", (RS, STOP_ROW_WORDS)),
+                                    d("stop_entries", (NS, STOP_ENT_WORDS)))
                 self.stop_steps += 1
             ev0 = self._start_event()
             te = time.perf_counter_ns()
             fwd = self._micro_forward if micro else self.model.forward
-            out = fwd(tok_d, d[T:2 * T], d[2 * T:3 * T], d[3 * T:o_dec].long(), tiles=til, n_dec=D, **skw)
-            if RS:
-                out, flags = out[:-1], out[-1]
-                out = out[0] if len(out) == 1 else out
-            if L:
-                out, lp, ids = out
+            out = fwd(tok_d, d("pos"), d("slot"), d("samp").long(), tiles=til, n_dec=D, **skw)
+            if L or RS:                                # (a ``HeadOut``: the tokens alone otherwise)
+                out, lp, ids, flags = out.tokens, out.lp, out.ids, out.stop_flags
             self.host_ns[2] += time.perf_counter_ns() - te
             if not micro:
                 self._census(T)

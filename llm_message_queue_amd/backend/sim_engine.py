@@ -87,7 +87,7 @@ class SimEngine(BackendEngine):
 
     @staticmethod
     def _forward(tok, pos, slot, samp, tiles=None, n_dec=0, inv_temp=None, keys=None, trunc=None, logp=None,
-                 pen=None):
+                 pen=None, stop=None):
         return torch.zeros(int(samp.shape[0]), dtype=torch.int32)
 
     def warm_shapes(self, sizes=None) -> int:

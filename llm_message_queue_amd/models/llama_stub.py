@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -77,6 +77,76 @@ class LlamaConfig:
 # the layer weights a ``quant`` forward reads as FP8 (e4m3 codes + a scale a row)
 QUANT_NAMES = ("wqkv", "wo", "w_gu", "w_down")
 QUANT_NAMES_BY_MODE = {"bf16": (), "fp8": QUANT_NAMES}
+
+
+def _given(**kw) -> dict:
+    """The keyword arguments that are set: a head is passed an optional input
+    only where a row of the step uses it, so a step without one makes the
+    call it made before the option existed."""
+    return {k: v for k, v in kw.items() if v is not None}
+
+
+class Truncate(NamedTuple):
+    """``forward(trunc=...)``: the sampled rows that ask for top-k / top-p /
+    min-p and are drawn again, from their own logits, by
+    ``ops.truncated_head`` (the head over all sampled rows runs as without
+    it; their first draw is overwritten)."""
+    rows: torch.Tensor                        # int64 [R] into the sampled rows
+    top_k: torch.Tensor                       # int32 [R] (0: none)
+    top_p: torch.Tensor                       # float32 [R] (1.0: none)
+    log_min_p: Optional[torch.Tensor] = None  # float32 [R] (``ops.sampling.min_p_log``; -inf: off) or None
+
+
+class LogitEdit(NamedTuple):
+    """The allow lists and logit biases of a step's edited rows
+    (``ops.gemm.logit_edit``)."""
+    ids: torch.Tensor                         # int32 [N]: the rows' lists, packed
+    vals: torch.Tensor                        # float32 [N]
+    spans: torch.Tensor                       # int32 [P][4]: (allow_off, n_allow, bias_off, n_bias) per row
+
+
+class Penalise(NamedTuple):
+    """``forward(pen=...)``: the device-side token history, the token rows of
+    this forward to record in it, and the sampled rows that ask for a
+    presence / frequency / repetition penalty, an allow-list or a logit bias,
+    greedy or sampling.  Those rows are drawn again by ``ops.penalised_head``
+    with their own ``top_k`` / ``top_p`` / ``log_min_p`` and overwrite their
+    first draw; the caller keeps them out of ``trunc``, so a row is drawn
+    again once.  A row with only an allow-list or a bias has a penalty span
+    whose slot is -1."""
+    hist: Optional[torch.Tensor]              # int32 [slots][max_ctx]; None where no slot has a penalty
+    #                                           (nothing is recorded or read then)
+    record: Optional[torch.Tensor]            # int32 [Q]: token rows of this forward to record in ``hist``
+    rows: torch.Tensor                        # int64 [P] into the sampled rows, the greedy ones first
+    spans: torch.Tensor                       # int32 [P][4]: (slot, from, split, end) in ``hist``
+    params: torch.Tensor                      # float32 [P][3]: presence, frequency, repetition
+    top_k: torch.Tensor                       # int32 [P]
+    top_p: torch.Tensor                       # float32 [P]
+    n_greedy: Optional[int]                   # so many of ``rows`` are greedy
+    edit: Optional[LogitEdit] = None
+    log_min_p: Optional[torch.Tensor] = None  # float32 [P] or None
+
+
+class Stops(NamedTuple):
+    """``forward(stop=...)``: the sampled rows that have stop tokens or stop
+    sequences (``csrc/kernels/stop_kernels.h``).  After the last overwrite
+    of the tokens ``ops.stop_match`` compares each such row's generated
+    tokens with its entries."""
+    hist: Optional[torch.Tensor]              # int32 [slots][max_ctx] or None (no entry longer than one token)
+    record: Optional[torch.Tensor]            # int32 [Q] token rows to record in ``hist`` where ``pen`` does not
+    #                                           already (the engine merges them into ``pen``'s list), or None
+    rows: torch.Tensor                        # int64 [R] into the sampled rows
+    records: torch.Tensor                     # int32 [R][6]: (slot, gen_from, end, min_tokens, ent_off, n_ent)
+    entries: torch.Tensor                     # int32 [N][9]: length, then up to 8 token ids
+
+
+class HeadOut(NamedTuple):
+    """What ``forward`` returns when ``logp`` or ``stop`` is given; the
+    fields not asked for are None."""
+    tokens: torch.Tensor                      # int32 [S]
+    lp: Optional[torch.Tensor]                # float32 [L][6]: the chosen token's score, then the 5 most likely
+    ids: Optional[torch.Tensor]               # int32 [L][5]
+    stop_flags: Optional[torch.Tensor]        # int32 [R]: the matched entry, -1: none
 
 
 class LlamaStub:
@@ -252,49 +322,27 @@ class LlamaStub:
                 small_cus: int = 0, inv_temp: Optional[torch.Tensor] = None,
                 keys: Optional[torch.Tensor] = None, quant: bool = False, trunc=None, logp=None, pen=None,
                 stop=None):
-        """One step over T tokens; returns greedy next-token ids for the rows
-        in ``sample_idx`` (the last token of each request's chunk).  With
-        ``inv_temp`` (float32, 1 / T per sampled row, 0 = greedy) and ``keys``
-        (``ops.sampling.row_keys``) the head samples instead
-        (``ops.sample_head``: temperature sampling by Gumbel-max).  ``trunc``
-        = (rows int64 [R] into the sampled rows, top_k int32 [R], top_p
-        float32 [R]): those rows ask for top-k / top-p and are drawn again,
-        from their own logits, by ``ops.truncated_head`` (the head over all
-        sampled rows runs as without it; their first draw is overwritten).  A
-        fourth element, log_min_p float32 [R] (``ops.sampling.min_p_log``; -inf:
-        off), adds ``min_p``.
-        ``logp`` (int64 [L] rows into the sampled rows, sampling or greedy):
-        those rows ask for log-probabilities; the result is then ``(tokens,
-        lp float32 [L][6], ids int32 [L][5])`` with ``ops.logprob_head``'s
-        scores of the tokens finally chosen, after the truncation overwrite
-        (the tokens themselves are what they are without it).
-        ``pen`` = (hist int32 [slots][max_ctx], rec int32 [Q], rows int64 [P],
-        spans int32 [P][4], params float32 [P][3], top_k int32 [P], top_p
-        float32 [P], n_greedy): the device-side token history, the token rows
-        of this forward to record in it (``ops.history_record``, before
-        anything reads it; a forward that samples nothing still records),
-        and the sampled rows that ask for a presence / frequency / repetition
-        penalty, greedy or sampling, the first ``n_greedy`` of them greedy.
-        Those rows are drawn again by ``ops.penalised_head`` with their own
-        ``top_k`` / ``top_p`` and overwrite their first draw; the caller keeps
-        them out of ``trunc``, so a row is drawn again once.  Two more
-        elements, ``edit`` = (ids int32 [N], vals float32 [N], spans int32
-        [P][4]) or None and log_min_p float32 [P] or None, carry the rows'
-        allow lists and logit biases (``ops.gemm.logit_edit``) and their
-        ``min_p``; rows with only those have a penalty span whose slot is -1,
-        and ``hist`` is None where no slot has a penalty (nothing is recorded
-        or read then).
-        ``stop`` = (hist int32 [slots][max_ctx] or None, rec int32 [Q] or None,
-        rows int64 [R] into the sampled rows, records int32 [R][6], ent int32
-        [N][9]): the sampled rows that have stop tokens or stop sequences
-        (``csrc/kernels/stop_kernels.h``).  ``rec`` names token rows to record
-        in ``hist`` where ``pen`` does not already (the engine merges them
-        into ``pen``'s list: the slots that hold an entry longer than one
-        token).  After the last overwrite of the tokens ``ops.stop_match``
-        compares each such row's generated tokens with its entries, and its
-        int32 [R] result (the matched entry, -1: none) is returned behind the
-        tokens, and behind ``lp, ids`` where ``logp`` is given too.  No token
-        is changed by it.
+        """One step over T tokens; returns the next-token ids (int32) of the
+        rows in ``sample_idx`` (the last token of each request's chunk).  In
+        this order:
+          1. the token rows ``pen.record`` / ``stop.record`` name are recorded
+             in the device history (``ops.history_record``), before anything
+             reads it; a forward that samples nothing still records;
+          2. the trunk (``hidden``);
+          3. the head over all sampled rows: with ``inv_temp`` (float32, 1 / T
+             per sampled row, 0 = greedy) and ``keys`` (``ops.sampling.
+             row_keys``) ``ops.sample_head`` (temperature sampling by
+             Gumbel-max), else ``ops.greedy_head``;
+          4. ``trunc`` (``Truncate``): its rows are drawn again, from their own
+             logits, and overwrite their first draw;
+          5. ``pen`` (``Penalise``): likewise, greedy or sampling;
+          6. ``stop`` (``Stops``): ``ops.stop_match`` over the tokens as they
+             now are.  No token is changed by it;
+          7. ``logp`` (int64 [L] rows into the sampled rows, sampling or
+             greedy): ``ops.logprob_head``'s scores of the tokens finally
+             chosen (the tokens themselves are what they are without it).
+        Returns the token tensor when neither ``logp`` nor ``stop`` is given,
+        else a ``HeadOut``.
         ``tiles`` (int32 [n, 4], see ``ops.llama_ops.make_tiles``) groups the
         tokens into per-slot segments for the MFMA attention kernel (its first
         ``n_dec`` rows are 1-token decode tiles); without it attention runs
@@ -305,10 +353,9 @@ class LlamaStub:
         where the tiles cannot fill the partition.  ``quant`` (a model built
         with ``small_weights="fp8"``): every layer GEMM of this forward reads
         the FP8 weights (``hidden``); the head stays bf16."""
-        if pen is not None and pen[0] is not None and pen[1].numel():
-            self.ops.history_record(pen[0], tokens, pos, slot, pen[1])
-        if stop is not None and stop[0] is not None and stop[1] is not None and stop[1].numel():
-            self.ops.history_record(stop[0], tokens, pos, slot, stop[1])
+        for opt in (pen, stop):
+            if opt is not None and opt.hist is not None and opt.record is not None and opt.record.numel():
+                self.ops.history_record(opt.hist, tokens, pos, slot, opt.record)
         if self.prune_last and self.residual_in_gemm:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus,
                               quant=quant)
@@ -316,38 +363,34 @@ class LlamaStub:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec,
                               small_cus=small_cus, quant=quant).index_select(0, sample_idx)
         hand = small_cus or not self.library_gemm
-        if inv_temp is not None and keys is not None:
+        sampling = inv_temp is not None and keys is not None
+        if sampling:
             out = self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
                                        min_rows=1 if hand else 256)
             if trunc is not None:
-                rows, top_k, top_p = trunc[:3]
-                kw = {"log_min_p": trunc[3]} if len(trunc) > 3 and trunc[3] is not None else {}
-                out.index_copy_(0, rows, self.ops.truncated_head(
-                    sel.index_select(0, rows), self.lm_head, inv_temp.index_select(0, rows),
-                    keys.index_select(0, rows), top_k, top_p, **kw))
+                out.index_copy_(0, trunc.rows, self.ops.truncated_head(
+                    sel.index_select(0, trunc.rows), self.lm_head, inv_temp.index_select(0, trunc.rows),
+                    keys.index_select(0, trunc.rows), trunc.top_k, trunc.top_p, **_given(log_min_p=trunc.log_min_p)))
         else:
             out = self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
-        if pen is not None and pen[2].numel():
-            hist, _, rows, spans, params, top_k, top_p, n_greedy = pen[:8]
-            kw = {}
-            if len(pen) > 8 and (pen[8] is not None or pen[9] is not None):
-                kw = {"edit": pen[8], "log_min_p": pen[9]}
-            P = rows.numel()
-            if inv_temp is not None and keys is not None:
-                it, kk = inv_temp.index_select(0, rows), keys.index_select(0, rows)
+        if pen is not None and pen.rows.numel():
+            P = pen.rows.numel()
+            if sampling:
+                it, kk = inv_temp.index_select(0, pen.rows), keys.index_select(0, pen.rows)
             else:                                     # an all-greedy step: no noise is read
                 it = torch.zeros(P, dtype=torch.float32, device=out.device)
                 kk = torch.zeros((P, 2), dtype=torch.int32, device=out.device)
-            out.index_copy_(0, rows, self.ops.penalised_head(
-                sel.index_select(0, rows), self.lm_head, it, kk, top_k, top_p, hist, spans, params,
-                n_greedy=n_greedy, **kw))
-        flags = None
+            out.index_copy_(0, pen.rows, self.ops.penalised_head(
+                sel.index_select(0, pen.rows), self.lm_head, it, kk, pen.top_k, pen.top_p, pen.hist, pen.spans,
+                pen.params, n_greedy=pen.n_greedy, **_given(edit=pen.edit, log_min_p=pen.log_min_p)))
+        if logp is None and stop is None:
+            return out
+        flags = lp = ids = None
         if stop is not None:
-            flags = self.ops.stop_match(out.index_select(0, stop[2]), stop[0], stop[3], stop[4])
-        if logp is None:
-            return out if stop is None else (out, flags)
-        lp, ids = self.ops.logprob_head(sel.index_select(0, logp), self.lm_head, out.index_select(0, logp))
-        return (out, lp, ids) if stop is None else (out, lp, ids, flags)
+            flags = self.ops.stop_match(out.index_select(0, stop.rows), stop.hist, stop.records, stop.entries)
+        if logp is not None:
+            lp, ids = self.ops.logprob_head(sel.index_select(0, logp), self.lm_head, out.index_select(0, logp))
+        return HeadOut(out, lp, ids, flags)
 
     @torch.no_grad()
     def hidden(self, tokens: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,

@@ -111,56 +111,51 @@ class HipOps:
         sc = torch.where(it != 0, lg.double() * it.double() - torch.log(e), lg.double())
         return torch.argmax(sc, dim=-1).to(torch.int32)
 
-    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p, log_min_p=None):
-        """Tokens of the LM head under top-k / top-p / min-p sampling (int32
-        [R]; ``ops.gemm.sample_truncated``; ``log_min_p`` float32 [R] or None:
-        ``ops.sampling.min_p_log``) for the rows that ask for it.  Their
-        logits come from the 256x256 tile kernel's store epilogue whatever R
-        is -- no split-K, no skinny kernel -- so a row's logits are the bf16
-        rounding of the fp32 accumulators the fused head scores and do not
-        depend on who shares the step; a shape the tile kernel refuses takes
-        ``F.linear``.  The logits live in the grow-only scratch cache."""
+    def _row_logits(self, x, w, entry: str):
+        """bf16 logits of the rows ``x`` for a row-wise head, in the grow-only
+        scratch entry ``entry``: the 256x256 tile kernel's store epilogue
+        whatever the row count -- no split-K, no skinny kernel -- so a row's
+        logits are the bf16 rounding of the fp32 accumulators the fused head
+        scores and do not depend on who shares the step.  A shape the tile
+        kernel refuses takes ``F.linear``, its columns padded to a multiple
+        of 8."""
         from . import gemm as G
         R, V = x.shape[0], w.shape[0]
         if G.supported(R, V, x.shape[1]):
-            buf, = G._scratch(x.device, _stream(x), "trunc", (R * V, 0, torch.empty, torch.bfloat16))
-            lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
-        else:
-            lg = torch.nn.functional.linear(x, w)
-            if V % 8:
-                lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
-            lg = lg.contiguous()
-        return G.sample_truncated(lg, inv_temp.contiguous(), keys.contiguous(), top_k, top_p, vocab=V,
+            buf, = G._scratch(x.device, _stream(x), entry, (R * V, 0, torch.empty, torch.bfloat16))
+            return G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
+        lg = torch.nn.functional.linear(x, w)
+        if V % 8:
+            lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
+        return lg.contiguous()
+
+    def truncated_head(self, x, w, inv_temp, keys, top_k, top_p, log_min_p=None):
+        """Tokens of the LM head under top-k / top-p / min-p sampling (int32
+        [R]; ``ops.gemm.sample_truncated``; ``log_min_p`` float32 [R] or None:
+        ``ops.sampling.min_p_log``) for the rows that ask for it, over their
+        own logits (``_row_logits``)."""
+        from . import gemm as G
+        lg = self._row_logits(x, w, "trunc")
+        return G.sample_truncated(lg, inv_temp.contiguous(), keys.contiguous(), top_k, top_p, vocab=w.shape[0],
                                   log_min_p=None if log_min_p is None else log_min_p.contiguous())
 
     def logprob_head(self, x, w, tok):
         """Log-probabilities of the LM head for the rows that ask for them:
         ``(lp float32 [L][6], ids int32 [L][5])`` of ``ops.gemm.
         token_logprobs`` -- the token ``tok`` (int32 [L]) first, then the 5
-        most likely.  The logits come as ``truncated_head``'s do (the tile
-        kernel's store epilogue whatever L is, ``F.linear`` for a shape it
-        refuses), in a scratch entry of their own, so a row's result depends
-        on nothing but the row."""
+        most likely.  The logits are the rows' own (``_row_logits``, a
+        scratch entry of their own), so a row's result depends on nothing but
+        the row."""
         from . import gemm as G
-        R, V = x.shape[0], w.shape[0]
-        if G.supported(R, V, x.shape[1]):
-            buf, = G._scratch(x.device, _stream(x), "logp", (R * V, 0, torch.empty, torch.bfloat16))
-            lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
-        else:
-            lg = torch.nn.functional.linear(x, w)
-            if V % 8:
-                lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
-            lg = lg.contiguous()
-        return G.token_logprobs(lg, tok.to(torch.int32).contiguous(), vocab=V)
+        lg = self._row_logits(x, w, "logp")
+        return G.token_logprobs(lg, tok.to(torch.int32).contiguous(), vocab=w.shape[0])
 
     def penalised_head(self, x, w, inv_temp, keys, top_k, top_p, hist, spans, params, n_greedy=None, edit=None,
                        log_min_p=None):
         """Tokens of the LM head (int32 [R]) for the edited rows: those that
         ask for a presence / frequency / repetition penalty, an allow-list or
-        a logit bias.  Their logits come as
-        ``truncated_head``'s do (the tile kernel's store epilogue whatever R
-        is, ``F.linear`` for a shape it refuses), in a scratch entry of their
-        own; ``ops.gemm.penalise`` edits them in place by each row's history
+        a logit bias.  Their logits are their own (``_row_logits``, a scratch
+        entry of their own); ``ops.gemm.penalise`` edits them in place by each row's history
         (``hist`` int32 [slots][max_ctx], ``spans`` int32 [R][4], ``params``
         float32 [R][3]: ``csrc/kernels/penalty_kernels.h``).  Then a row with
         ``inv_temp > 0`` is drawn by ``ops.gemm.sample_truncated`` under its
@@ -190,14 +185,7 @@ class HipOps:
                     edit = (edit[0], edit[1], edit[2][:R].index_select(0, order))
                 if log_min_p is not None:
                     log_min_p = log_min_p[:R].index_select(0, order)
-        if G.supported(R, V, x.shape[1]):
-            buf, = G._scratch(x.device, _stream(x), "pen", (R * V, 0, torch.empty, torch.bfloat16))
-            lg = G.gemm(x.contiguous(), w, out=buf[:R * V].view(R, V))
-        else:
-            lg = torch.nn.functional.linear(x, w)
-            if V % 8:
-                lg = torch.nn.functional.pad(lg, (0, 8 - V % 8))
-            lg = lg.contiguous()
+        lg = self._row_logits(x, w, "pen")
         if hist is not None:
             G.penalise(lg, hist, spans.contiguous(), params.contiguous(), vocab=V)
         if edit is not None:
@@ -371,19 +359,30 @@ class RefOps:
         from .sampling import sample_reference
         M = x.shape[0]
         lg = (x.float() @ w.float().t()).cpu().numpy()
-        kk = keys[:M].cpu().contiguous().view(torch.int32).numpy().view("uint32")
+        kk = self._keys(keys, M)
         it = inv_temp[:M]
         picks = torch.from_numpy(sample_reference(lg, it.cpu().numpy(), kk)).to(x.device)
         # a greedy row is exactly this class's greedy_head (bf16 logits)
         return torch.where(it != 0, picks, self.greedy_head(x, w, fused, min_rows))
+
+    @staticmethod
+    def _bf16_logits(x, w):
+        """The rows' logits as ``HipOps._row_logits`` stores them: fp32
+        products rounded to bf16 (a CPU tensor)."""
+        return (x.float() @ w.float().t()).to(torch.bfloat16).cpu().contiguous()
+
+    @staticmethod
+    def _keys(keys, R):
+        """The first ``R`` row keys as the numpy twins take them (uint32 [R][2])."""
+        return keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
 
     def truncated_head(self, x, w, inv_temp, keys, top_k, top_p, log_min_p=None):
         """Reference of ``HipOps.truncated_head``: fp32 logits rounded to bf16,
         then the numpy twin (``ops.sampling.sample_truncated_reference``)."""
         from .sampling import sample_truncated_reference
         R = x.shape[0]
-        lg = (x.float() @ w.float().t()).to(torch.bfloat16).float().cpu().numpy()
-        kk = keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
+        lg = self._bf16_logits(x, w).float().numpy()
+        kk = self._keys(keys, R)
         picks = sample_truncated_reference(lg, inv_temp[:R].cpu().numpy(), kk, top_k[:R].cpu().numpy(),
                                            top_p[:R].cpu().numpy(),
                                            log_min_p=None if log_min_p is None else log_min_p[:R].cpu().numpy())
@@ -393,8 +392,7 @@ class RefOps:
         """Reference of ``HipOps.logprob_head``: fp32 logits rounded to bf16,
         then the numpy twin in float64 (``ops.sampling.logprob_reference``)."""
         from .sampling import logprob_reference
-        lg = (x.float() @ w.float().t()).to(torch.bfloat16).float().cpu().numpy()
-        lp, ids = logprob_reference(lg, tok.cpu().numpy())
+        lp, ids = logprob_reference(self._bf16_logits(x, w).float().numpy(), tok.cpu().numpy())
         return (torch.from_numpy(lp.astype("float32")).to(x.device),
                 torch.from_numpy(ids.astype("int32")).to(x.device))
 
@@ -408,8 +406,7 @@ class RefOps:
         from .sampling import (bf16_values, logit_edit_reference, penalise_rows_reference, penalised_pick_reference,
                                sample_truncated_reference)
         R, V = x.shape[0], w.shape[0]
-        lg = (x.float() @ w.float().t()).to(torch.bfloat16).cpu().contiguous()
-        bits = lg.view(torch.int16).numpy().view("uint16")
+        bits = self._bf16_logits(x, w).view(torch.int16).numpy().view("uint16")
         if hist is not None:
             bits = penalise_rows_reference(bits, V, hist.cpu().numpy(), spans[:R].cpu().numpy(),
                                            params[:R].cpu().numpy())
@@ -420,8 +417,7 @@ class RefOps:
         picks = penalised_pick_reference(bits, V)
         hot = it > 0
         if hot.any():
-            kk = keys[:R].cpu().contiguous().view(torch.int32).numpy().view("uint32")
-            picks[hot] = sample_truncated_reference(bf16_values(bits)[hot], it[hot], kk[hot],
+            picks[hot] = sample_truncated_reference(bf16_values(bits)[hot], it[hot], self._keys(keys, R)[hot],
                                                     top_k[:R].cpu().numpy()[hot], top_p[:R].cpu().numpy()[hot],
                                                     log_min_p=None if log_min_p is None
                                                     else log_min_p[:R].cpu().numpy()[hot])

@@ -162,7 +162,7 @@ def test_forward_with_stop_on_the_tiny_model():
     """The returned flags are the twin's over the returned tokens and the
     history the forward recorded; the tokens are what they are without
     ``stop``."""
-    from llm_message_queue_amd.models.llama_stub import LlamaConfig, LlamaStub
+    from llm_message_queue_amd.models.llama_stub import LlamaConfig, LlamaStub, Stops
     m = LlamaStub(LlamaConfig.tiny(), 4, 32, device=torch.device(DEV), impl="hip", seed=0)
     i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)     # noqa: E731
     tok = torch.tensor([5, 6, 7, 8, 9], dtype=torch.long, device=DEV)
@@ -178,16 +178,19 @@ def test_forward_with_stop_on_the_tiny_model():
     ent = torch.from_numpy(S.stop_table([[a0[0]], [a0[0], a1[0]], [1 << 20], [9, a0[1], a1[1]], [a0[1], a1[1]]])).to(DEV)
     hist = torch.full((4, 32), -5, dtype=torch.int32, device=DEV)
     rows0 = i32([[0, 3, 3, 0, 0, 2], [2, 2, 2, 0, 2, 3]])
-    out, flags = m.forward(tok, pos, slot, samp, stop=(hist, i32([0, 1, 2, 3, 4]), s1, rows0, ent))
+    res = m.forward(tok, pos, slot, samp, stop=Stops(hist, i32([0, 1, 2, 3, 4]), s1, rows0, ent))
     torch.cuda.synchronize()
+    assert res.lp is None and res.ids is None
+    out, flags = res.tokens, res.stop_flags
     assert out.cpu().tolist() == a0 and flags.dtype == torch.int32
     want0 = S.stop_match_reference(out.cpu().numpy(), hist.cpu().numpy(), rows0.cpu().numpy(), ent.cpu().numpy())
     assert flags.cpu().tolist() == want0.tolist() == [0, -1]
     assert hist[0, :3].cpu().tolist() == [5, 6, 7] and hist[2, :2].cpu().tolist() == [8, 9] and int(hist[0, 3]) == -5
     rows1 = i32([[0, 3, 4, 0, 1, 1], [2, 2, 3, 0, 2, 3]])
-    out, lp, ids, flags = m.forward(out.long(), pos1, slot1, s1, logp=torch.tensor([1], device=DEV),
-                                    stop=(hist, i32([0, 1]), s1, rows1, ent))
+    res = m.forward(out.long(), pos1, slot1, s1, logp=torch.tensor([1], device=DEV),
+                    stop=Stops(hist, i32([0, 1]), s1, rows1, ent))
     torch.cuda.synchronize()
+    out, lp, ids, flags = res.tokens, res.lp, res.ids, res.stop_flags
     assert out.cpu().tolist() == a1 and lp.shape == (1, 6) and ids.shape == (1, 5)
     assert int(hist[0, 3]) == a0[0] and int(hist[2, 2]) == a0[1]       # the decode rows' tokens, recorded before the head
     want1 = S.stop_match_reference(out.cpu().numpy(), hist.cpu().numpy(), rows1.cpu().numpy(), ent.cpu().numpy())

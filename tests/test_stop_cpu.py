@@ -583,7 +583,7 @@ def test_without_the_keys_the_staging_buffer_and_the_launches_are_what_they_were
 
 def test_forward_with_stop_returns_the_flags_beside_the_tokens():
     import torch
-    from llm_message_queue_amd.models.llama_stub import LlamaConfig, LlamaStub
+    from llm_message_queue_amd.models.llama_stub import HeadOut, LlamaConfig, LlamaStub, Stops
     m = LlamaStub(LlamaConfig.tiny(), 4, 32, device=torch.device("cpu"), impl="ref", seed=0)
     tok = torch.tensor([5, 6, 7, 8, 9], dtype=torch.long)
     pos = torch.tensor([0, 1, 2, 0, 1], dtype=torch.int32)
@@ -596,13 +596,18 @@ def test_forward_with_stop_returns_the_flags_beside_the_tokens():
     ent = torch.from_numpy(stop_table([[7, t0[0]], [t0[1]], [8, 9, t0[1]]]))
     rows = torch.tensor([[0, 2, 3, 0, 0, 1], [2, 0, 2, 0, 1, 2]], dtype=torch.int32)
     rec = torch.tensor([2, 3, 4], dtype=torch.int32)
-    out, flags = m.forward(tok, pos, slot, samp, stop=(hist, rec, torch.tensor([0, 1]), rows, ent))
+    res = m.forward(tok, pos, slot, samp, stop=Stops(hist, rec, torch.tensor([0, 1]), rows, ent))
+    assert isinstance(res, HeadOut) and res.lp is None and res.ids is None
+    out, flags = res.tokens, res.stop_flags
     assert out.tolist() == t0 and flags.dtype == torch.int32 and flags.tolist() == [0, 0]
     assert hist[0, 2] == 7 and hist[2, 0] == 8 and hist[2, 1] == 9 and hist[0, 0] == -1
     rows[1, 4], rows[1, 5] = 2, 1                                       # only the three-token entry
-    out, lp, ids, flags = m.forward(tok, pos, slot, samp, logp=torch.tensor([1]),
-                                    stop=(hist, rec, torch.tensor([1]), rows[1:].contiguous(), ent))
-    assert out.tolist() == t0 and flags.tolist() == [0] and lp.shape == (1, 6)
+    res = m.forward(tok, pos, slot, samp, logp=torch.tensor([1]),
+                    stop=Stops(hist, rec, torch.tensor([1]), rows[1:].contiguous(), ent))
+    assert res.tokens.tolist() == t0 and res.stop_flags.tolist() == [0] and res.lp.shape == (1, 6)
+    assert res.ids.shape == (1, 5)
+    res = m.forward(tok, pos, slot, samp, logp=torch.tensor([1]))
+    assert res.tokens.tolist() == t0 and res.lp.shape == (1, 6) and res.stop_flags is None
 
 
 # --------------------------------------------------------------------------- the gateway, one rank and two

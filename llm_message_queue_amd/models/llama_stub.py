@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from ..ops import gemm as G
 from ..ops import quant as Qn
 from ..ops.llama_ops import get_ops, rope_tables
+from . import routes as R
 
 
 @dataclass
@@ -235,6 +236,7 @@ class LlamaStub:
                 self.fused_mlp and self.fused_qkv and self.row_scale_norm and self.residual_in_gemm):
             raise ValueError("small_weights fp8 needs the fused paths (fused_mlp, fused_qkv, row_scale_norm, "
                              "residual_in_gemm)")
+        self.route_flags = self._route_flags()
         g = torch.Generator(device=self.device).manual_seed(seed)
         std = 0.02
 
@@ -273,6 +275,16 @@ class LlamaStub:
                        for _ in range(cfg.layers)]
         self.cos, self.sin = rope_tables(max_ctx, cfg.rope_theta, self.device)
         self.scale = 1.0 / math.sqrt(hd)
+
+    def _route_flags(self) -> R.RouteFlags:
+        """What ``models.routes`` plans from, read once when the model is built."""
+        cfg = self.cfg
+        return R.RouteFlags(
+            hip=self.impl == "hip", residual_in_gemm=bool(self.residual_in_gemm), split_qkv=bool(self.split_qkv),
+            fused_mlp=self.fused_mlp, fused_qkv=self.fused_qkv, row_scale_norm=self.row_scale_norm,
+            fused_rms=self.fused_rms, prune_last=self.prune_last, library_gemm=self.library_gemm,
+            min_fused_tokens=self.min_fused_tokens, min_fused_qkv_tokens=self.min_fused_qkv_tokens, cus=self._cus,
+            dim=cfg.dim, n_qkv=(cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim)
 
     @staticmethod
     def _fold_norm(w: torch.Tensor, g: torch.Tensor):
@@ -356,23 +368,23 @@ class LlamaStub:
         for opt in (pen, stop):
             if opt is not None and opt.hist is not None and opt.record is not None and opt.record.numel():
                 self.ops.history_record(opt.hist, tokens, pos, slot, opt.record)
-        if self.prune_last and self.residual_in_gemm:
+        step = R.plan_step(self.route_flags, small_cus)
+        if step.prune:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec, rows=sample_idx, small_cus=small_cus,
                               quant=quant)
         else:
             sel = self.hidden(tokens, pos, slot, tiles=tiles, n_dec=n_dec,
                               small_cus=small_cus, quant=quant).index_select(0, sample_idx)
-        hand = small_cus or not self.library_gemm
         sampling = inv_temp is not None and keys is not None
         if sampling:
             out = self.ops.sample_head(sel, self.lm_head, inv_temp, keys, self.fused_head,
-                                       min_rows=1 if hand else 256)
+                                       min_rows=step.head_min_rows)
             if trunc is not None:
                 out.index_copy_(0, trunc.rows, self.ops.truncated_head(
                     sel.index_select(0, trunc.rows), self.lm_head, inv_temp.index_select(0, trunc.rows),
                     keys.index_select(0, trunc.rows), trunc.top_k, trunc.top_p, **_given(log_min_p=trunc.log_min_p)))
         else:
-            out = self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=1 if hand else 256)
+            out = self.ops.greedy_head(sel, self.lm_head, self.fused_head, min_rows=step.head_min_rows)
         if pen is not None and pen.rows.numel():
             P = pen.rows.numel()
             if sampling:
@@ -404,6 +416,9 @@ class LlamaStub:
         the qkv and gate/up projections are never materialised: ``row_rms``
         computes each row's scale, the norm weight is folded into W at init,
         and the GEMM epilogue applies the scale to its accumulator rows.
+        Which kernel each GEMM takes is planned by ``models.routes``, three
+        plans a step: the qkv projection, a layer's o + MLP block at the
+        step's rows, and the last layer's block at the rows it keeps.
 
         ``rows`` (the step's sampled rows): the last layer writes every
         token's K/V and attends for every token as usual, then keeps only
@@ -425,64 +440,26 @@ class LlamaStub:
         layers = self.layers
         if quant and self.impl != "hip":
             layers, quant = [self._dequantized(i) for i in range(len(self.layers))], False
-        if not self.residual_in_gemm:
+        f = self.route_flags
+        if R.plan_step(f, small_cus).residual_norm:
             return self._hidden_residual_norm(tokens, pos, slot, tiles, n_dec, layers)
         res = F.embedding(tokens, self.embed)            # [T, d], updated in place
         T = res.shape[0]
-        if quant and T > G.SKINNY_CHUNKED_MAX_M:
-            raise ValueError(f"quant forward of {T} rows: the fp8 kernel takes at most {G.SKINNY_CHUNKED_MAX_M}")
-        small = small_cus > 0 and self.impl == "hip"
-        nolib = not self.library_gemm and self._cus > 0
-        # the skinny kernel (a stream over the weights) for qkv up to
-        # SKINNY_PROJ_MAX_M rows; larger steps: the 256x256-tile kernel, split-K
-        # (profiles/r6_skinny_chunked.jsonl)
-        # (on a micro-forward's CU partition only up to SKINNY_MAX_M: there the
-        # split-K tiles were faster for larger steps; only with the norm weight
-        # folded into wqkv, fused_qkv: the kernel applies the row scale alone)
-        skinny = (small or nolib) and T <= (G.SKINNY_MAX_M if small else G.SKINNY_PROJ_MAX_M) \
-            and self.row_scale_norm and self.fused_mlp and self.fused_qkv
-        sk_cus = small_cus if small else self._cus
-        rows_qkv = self.fused_qkv and (T >= self.min_fused_qkv_tokens or small or nolib)
-        qkv_split = {}
-        if small or nolib:
-            d = cfg.dim
-            f = G.split_all(T, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim, d, sk_cus)
-            # every tile split when twice the tiles fit one wave; else the
-            # default half-empty-last-wave plan (split_plan)
-            qkv_split = {"split": True, "split_full": f} if f is not None else {}
-        last = len(layers) - 1
         if rows is not None and rows.numel() == T:
             rows = None                                  # every row sampled: nothing to drop
+        qkv = R.plan_qkv(f, T, small_cus, quant)         # (refuses a quant step the fp8 kernel cannot take)
+        block = R.plan_block(f, T, small_cus, quant)
+        tail = R.plan_block(f, T if rows is None else rows.numel(), small_cus, quant, last=True)
+        last = len(layers) - 1
 
         scale = None                                     # row scales of res from the previous down GEMM
         for i, L in enumerate(layers):
-            if quant or skinny:
-                qkv = torch.empty((T, L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
-                rs = ops.row_rms(res, cfg.eps)
-                if quant and G.fp8_plan(T, "qkv", small) == "tile":
-                    G.gemm_fp8(res, *L["fp8"]["wqkv"], out=qkv, row_scale=rs, split_cus=sk_cus)
-                elif quant:
-                    G.skinny_fp8(res, *L["fp8"]["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=sk_cus or 32)
-                else:
-                    G.skinny(res, L["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=sk_cus)
-                q = ops.rope_kv(qkv, pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i],
-                                self.vcache[i])
-            elif rows_qkv and self.row_scale_norm:
-                q = ops.qkv_rope_rows(res, L["wqkv"], scale if scale is not None else ops.row_rms(res, cfg.eps),
-                                      pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i],
-                                      self.vcache[i], **qkv_split)
-            elif rows_qkv:
-                q = G.qkv_rope(ops.rmsnorm(res, L["attn_norm"], cfg.eps), L["wqkv"], pos, slot, self.cos,
-                               self.sin, cfg.heads, cfg.kv_heads, self.kcache[i], self.vcache[i])
-            else:
-                q = self._qkv(ops.rmsnorm(res, L["attn_norm"], cfg.eps), L, i, pos, slot)
-            a = self._attend(q, i, pos, slot, tiles, n_dec)
+            a = self._attend(self._qkv_proj(qkv, res, scale, L, i, pos, slot), i, pos, slot, tiles, n_dec)
             if i == last and rows is not None:
                 if rows.numel() == 0:                    # nothing sampled (a step of unfinished prefill
                     return res[:0]                       # chunks): K/V written, no row kernel gets 0 rows
                 res, a = res.index_select(0, rows), a.index_select(0, rows)
-            scale = self._mlp_block(res, a, L, want_scale=rows_qkv and self.row_scale_norm and i < last,
-                                    small_cus=small_cus if small else 0, quant=quant)
+            scale = self._mlp_block(res, a, L, tail if i == last else block)
         return ops.rmsnorm(res, self.final_norm, cfg.eps)
 
     @torch.no_grad()
@@ -499,86 +476,88 @@ class LlamaStub:
             M = int(M)
             res = torch.zeros((M, cfg.dim), dtype=self.embed.dtype, device=self.device)
             a = torch.zeros((M, cfg.heads * cfg.head_dim), dtype=self.embed.dtype, device=self.device)
-            self._mlp_block(res, a, L)
+            self._mlp_block(res, a, L, R.plan_block(self.route_flags, M, 0, False, last=True))
             n += 1
         return n
 
-    def _mlp_block(self, res: torch.Tensor, a: torch.Tensor, L: dict, want_scale: bool = False,
-                   small_cus: int = 0, quant: bool = False):
-        """res += o(a); res += down(swiglu(norm(res))) -- in place, with the
-        fused-path choices made for this block's row count.  Returns the
-        RMSNorm row scales of the final ``res`` when ``want_scale`` and the
-        down GEMM produced them in its epilogue (``fused_rms``), else None.
-        ``small_cus``: a micro-forward's small step on its CU partition --
-        the hand-written kernels at any row count, split-K (``forward``).
-        ``quant``: o, gate/up and down on the FP8 weights in ``L["fp8"]``
-        (``skinny_fp8`` or the FP8-weight tile kernel, as ``ops.gemm.fp8_plan``
-        says for this block's row count)."""
+    def _row_scale(self, p: R.Gemm, res: torch.Tensor, carried):
+        """The RMSNorm row scales of ``res`` for GEMM ``p``: the ones the GEMM
+        before it made in its epilogue, where there are any and ``p`` takes
+        them, else a ``row_rms`` pass."""
+        return carried if p.takes_scale and carried is not None else self.ops.row_rms(res, self.cfg.eps)
+
+    def _qkv_proj(self, p: R.Gemm, res, scale, L, i, pos, slot):
+        """Layer ``i``'s rotated q of the rows ``res`` (K/V written into the
+        cache) on the kernel ``p`` names; ``scale``: the row scales the
+        previous layer's down GEMM made, or None."""
         cfg, ops = self.cfg, self.ops
-        M = res.shape[0]
-        small = small_cus > 0
-        if quant:
-            cus = small_cus or self._cus or 32
-            split = small_cus or self._cus               # the tile kernel's split-K plan: as the bf16 branch
-
-            def into_res_fp8(x, name, gemm):             # res += x · W[name]ᵀ on the kernel fp8_plan names
-                if G.fp8_plan(M, gemm, small) == "tile":
-                    G.gemm_residual_fp8(x, *L["fp8"][name], res, split_cus=split)
-                else:
-                    G.skinny_fp8(x, *L["fp8"][name], res, G.SK_RESID, cus=cus)
-
-            into_res_fp8(a, "wo", "o")
-            act = torch.empty((M, L["w_gu"].shape[0] // 2), dtype=res.dtype, device=res.device)
-            rs = ops.row_rms(res, cfg.eps)
-            if G.fp8_plan(M, "gu", small) == "tile":
-                G.gemm_swiglu_fp8(res, *L["fp8"]["w_gu"], out=act, row_scale=rs, split_cus=split)
-            else:
-                G.skinny_fp8(res, *L["fp8"]["w_gu"], act, G.SK_SWIGLU, row_scale=rs, cus=cus)
-            into_res_fp8(act, "w_down", "down")
-            return None
-        # library-free (``library_gemm`` False): the hand-written kernels at
-        # every row count, split-K where whole tiles leave CUs idle
-        nolib = not small and not self.library_gemm and self._cus > 0
-        cus = small_cus if small else (self._cus if nolib else 0)
-        rows_mlp = self.fused_mlp and (M >= self.min_fused_tokens or small or nolib)
-        tiles_ok = self._cus > 0 and G.residual_tiles_ok(M, cfg.dim, self._cus)
-        resid_o = small or nolib or tiles_ok
-        rms = tiles_ok and self.fused_rms and G.RESID_EPI == G.EPI_RESID_LDS and not small
-
-        # skinny: o / down up to SKINNY_RESID_MAX_M rows (past 256 its 128-row
-        # chunks still beat 256x256 tiles whose 32-64 tiles leave most CUs
-        # idle: profiles/r6_skinny_mid_m.jsonl), gate/up (N = 28,672: enough
-        # tiles to fill the chip) only up to SKINNY_MAX_M
-        skinny = (small or nolib) and M <= (G.SKINNY_MAX_M if small else G.SKINNY_RESID_MAX_M) \
-            and self.row_scale_norm and self.fused_mlp
-        skinny_gu = skinny and M <= G.SKINNY_MAX_M
-
-        def into_res(x, wt, scale_out):                  # res += x · wtᵀ (+ its row scales)
-            if rms and scale_out:
-                return G.gemm_residual_rms(x, wt, res, cfg.eps)
-            if skinny:
-                G.skinny(x, wt, res, G.SK_RESID, cus=cus)
-            elif resid_o:
-                G.gemm_residual(x, wt, res, split_cus=cus if (small or not tiles_ok) else 0)
-            else:
-                res.addmm_(x, wt.t())
-            return None
-
-        scale = into_res(a, L["wo"], rows_mlp and self.row_scale_norm)
-        if skinny_gu:
-            act = torch.empty((M, L["w_gu"].shape[0] // 2), dtype=res.dtype, device=res.device)
-            G.skinny(res, L["w_gu"], act, G.SK_SWIGLU, row_scale=ops.row_rms(res, cfg.eps), cus=cus)
-        elif rows_mlp and self.row_scale_norm and (small or nolib):
-            act = G.gemm_swiglu(res, L["w_gu"], row_scale=scale if scale is not None else ops.row_rms(res, cfg.eps),
-                                split_cus=cus)
-        elif rows_mlp and self.row_scale_norm:
-            act = ops.swiglu_rows(res, L["w_gu"], scale if scale is not None else ops.row_rms(res, cfg.eps))
-        elif rows_mlp:
-            act = G.gemm_swiglu(ops.rmsnorm(res, L["mlp_norm"], cfg.eps), L["w_gu"])
+        kv = (pos, slot, self.cos, self.sin, cfg.heads, cfg.kv_heads, self.kcache[i], self.vcache[i])
+        if p.kind == "tile_rows":
+            return ops.qkv_rope_rows(res, L["wqkv"], self._row_scale(p, res, scale), *kv, split_full=p.split_full)
+        if p.kind == "tile_normed":
+            return G.qkv_rope(ops.rmsnorm(res, L["attn_norm"], cfg.eps), L["wqkv"], *kv)
+        if p.kind == "library":
+            return self._qkv(ops.rmsnorm(res, L["attn_norm"], cfg.eps), L, i, pos, slot)
+        qkv = torch.empty((res.shape[0], L["wqkv"].shape[0]), dtype=res.dtype, device=res.device)
+        rs = self._row_scale(p, res, scale)
+        if p.kind == "tile_fp8":
+            G.gemm_fp8(res, *L["fp8"]["wqkv"], out=qkv, row_scale=rs, split_cus=p.split_cus)
+        elif p.kind == "skinny_fp8":
+            G.skinny_fp8(res, *L["fp8"]["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=p.cus)
+        elif p.kind == "skinny":
+            G.skinny(res, L["wqkv"], qkv, G.SK_STORE, row_scale=rs, cus=p.cus)
         else:
-            act = ops.mlp_up(ops.rmsnorm(res, L["mlp_norm"], cfg.eps), L["w_gu"], self.fused_mlp,
-                             self.min_fused_tokens)
-        return into_res(act, L["w_down"], want_scale)
+            raise ValueError(f"no qkv kernel of kind {p.kind!r}")
+        return ops.rope_kv(qkv, *kv)
+
+    def _into_res(self, p: R.Gemm, x, L, name: str, res):
+        """res += x . L[name]^T in place on the kernel ``p`` names; returns
+        the RMSNorm row scales of the updated ``res`` where ``p`` makes them,
+        else None."""
+        if p.kind == "tile_rms":
+            return G.gemm_residual_rms(x, L[name], res, self.cfg.eps)
+        if p.kind == "skinny":
+            G.skinny(x, L[name], res, G.SK_RESID, cus=p.cus)
+        elif p.kind == "tile":
+            G.gemm_residual(x, L[name], res, split_cus=p.split_cus)
+        elif p.kind == "library":
+            res.addmm_(x, L[name].t())
+        elif p.kind == "tile_fp8":
+            G.gemm_residual_fp8(x, *L["fp8"][name], res, split_cus=p.split_cus)
+        elif p.kind == "skinny_fp8":
+            G.skinny_fp8(x, *L["fp8"][name], res, G.SK_RESID, cus=p.cus)
+        else:
+            raise ValueError(f"no o / down kernel of kind {p.kind!r}")
+        return None
+
+    def _mlp_block(self, res: torch.Tensor, a: torch.Tensor, L: dict, plan: R.Block):
+        """res += o(a); res += down(swiglu(norm(res))) -- in place, each GEMM
+        on the kernel ``plan`` (``routes.plan_block`` for this block's row
+        count) names.  Returns the RMSNorm row scales of the final ``res``
+        where the down GEMM made them in its epilogue, else None."""
+        cfg, ops = self.cfg, self.ops
+        scale = self._into_res(plan.o, a, L, "wo", res)
+        p, w = plan.gu, L["w_gu"]
+        if p.kind in ("skinny", "skinny_fp8", "tile_fp8"):
+            act = torch.empty((res.shape[0], w.shape[0] // 2), dtype=res.dtype, device=res.device)
+            rs = self._row_scale(p, res, scale)
+            if p.kind == "tile_fp8":
+                G.gemm_swiglu_fp8(res, *L["fp8"]["w_gu"], out=act, row_scale=rs, split_cus=p.split_cus)
+            elif p.kind == "skinny_fp8":
+                G.skinny_fp8(res, *L["fp8"]["w_gu"], act, G.SK_SWIGLU, row_scale=rs, cus=p.cus)
+            else:
+                G.skinny(res, w, act, G.SK_SWIGLU, row_scale=rs, cus=p.cus)
+        elif p.kind == "tile_split":
+            act = G.gemm_swiglu(res, w, row_scale=self._row_scale(p, res, scale), split_cus=p.split_cus)
+        elif p.kind == "rows":
+            act = ops.swiglu_rows(res, w, self._row_scale(p, res, scale))
+        elif p.kind == "tile_normed":
+            act = G.gemm_swiglu(ops.rmsnorm(res, L["mlp_norm"], cfg.eps), w)
+        elif p.kind == "mlp_up":
+            act = ops.mlp_up(ops.rmsnorm(res, L["mlp_norm"], cfg.eps), w, self.fused_mlp, self.min_fused_tokens)
+        else:
+            raise ValueError(f"no gate/up kernel of kind {p.kind!r}")
+        return self._into_res(plan.down, act, L, "w_down", res)
 
     def _qkv(self, x, L, i, pos, slot):
         """qkv projection (hipBLASLt) + RoPE / KV-cache write of normalised rows."""

@@ -45,13 +45,18 @@ def test_kv_move_pack_unpack_bit_exact(max_ctx, cases, variant):
                            for L in range(cfg.layers)])
         assert buf.shape == ref.shape and torch.equal(buf, ref)
         dst = (slot + 1) % 6
-        before = [t[dst].clone() for t in m.kcache]
+        before_k = [t.clone() for t in m.kcache]
+        before_v = [t.clone() for t in m.vcache]
         mig.unpack(buf, dst)
         torch.cuda.synchronize()
+        others = [s for s in range(6) if s != dst]           # (the source slot among them)
         for L in range(cfg.layers):
             assert torch.equal(m.kcache[L][dst, :, :n], m.kcache[L][slot, :, :n])
             assert torch.equal(m.vcache[L][dst, :, :n], m.vcache[L][slot, :, :n])
-            assert torch.equal(m.kcache[L][dst, :, n:], before[L][:, n:])     # nothing past n touched
+            # nothing past n touched, in K or V, and no other slot at all: the same bits as before
+            for cache, before in ((m.kcache[L], before_k[L]), (m.vcache[L], before_v[L])):
+                assert torch.equal(cache[dst, :, n:].view(torch.int16), before[dst, :, n:].view(torch.int16))
+                assert torch.equal(cache[others].view(torch.int16), before[others].view(torch.int16))
 
 
 def test_rccl_self_p2p_migration_is_async_under_queued_8b_forwards():
